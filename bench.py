@@ -303,11 +303,12 @@ class Leg:
 
 
 def stgcn_leg(args, mfma, steps, warmup, warm_seconds, rank, world, dev, isolated_pass, first_run=False, instrument_steps=0,
-              classes=None, stream="joint", sustained_steps=0):
+              classes=None, stream="joint", sustained_steps=0, dump_dir=None):
     """ST-GCN train step (main_gnn.py:219-239) in one arithmetic mode; returns the result dict of rank 0 (None elsewhere).
     instrument_steps = 0: the per-kernel HIP events are recorded inside the timed region (the headline leg, as in every
     round); > 0: the timed region runs bare and that many extra steps are instrumented afterwards (long secondary legs:
-    two event records per launch are not free on a 7-15 ms step)."""
+    two event records per launch are not free on a 7-15 ms step).  dump_dir: rank 0 writes the outputs of the last timed step
+    there (write_outputs)."""
     import torch
     import torch.distributed as dist
     from sar_amd import profiler
@@ -325,7 +326,7 @@ def stgcn_leg(args, mfma, steps, warmup, warm_seconds, rank, world, dev, isolate
     leg = Leg(world, dev)
 
     def step(i):
-        return trainer.step(*batches[i % nb])[1]
+        return trainer.step(*batches[i % nb])
 
     first = None
     if first_run:     # the rate of a cool GPU (what a short run sees): 10 warm-up steps (allocator, lazy initialisation) + 20
@@ -339,6 +340,8 @@ def stgcn_leg(args, mfma, steps, warmup, warm_seconds, rank, world, dev, isolate
         profiler.install(timer)
     res = leg.run(step, steps, 0, 0.0, trainer)
     profiler.install(None)
+    if dump_dir and rank == 0:
+        write_outputs(dump_dir, timed_outputs(res["last"], eng))
     ksteps = steps
     if instrument_steps > 0:
         profiler.install(timer)
@@ -347,7 +350,7 @@ def stgcn_leg(args, mfma, steps, warmup, warm_seconds, rank, world, dev, isolate
         ksteps = instrument_steps
     res["warm_s"] = warm_s
     dt = res["dt"]
-    loss_val = float(res["last"].item())
+    loss_val = float(res["last"][1].item())
     assert loss_val == loss_val, "loss is NaN"
     sustained = None
     if sustained_steps > 0:      # the same protocol over a longer region, right behind the contract's K steps (bare: no per-kernel events)
@@ -459,9 +462,10 @@ def stgcn_leg(args, mfma, steps, warmup, warm_seconds, rank, world, dev, isolate
     return out                   #  hipMalloc for every tensor of its first steps)
 
 
-def spectrogram_leg(args, steps, warmup, warm_seconds, rank, world, dev, instrument_steps=0, num_pad_frames=None, mfma="fp32"):
+def spectrogram_leg(args, steps, warmup, warm_seconds, rank, world, dev, instrument_steps=0, num_pad_frames=None, mfma="fp32",
+                    dump_dir=None):
     """Path B: VirtualRadar (signal + STFT/log-magnitude/column select) -> resnet18 fwd+bwd -> Adam; bs = --batch per GPU
-    (configs[3] uses 32)."""
+    (configs[3] uses 32).  dump_dir: as in stgcn_leg."""
     import torch
     import torch.distributed as dist
     from sar_amd import profiler
@@ -481,13 +485,15 @@ def spectrogram_leg(args, steps, warmup, warm_seconds, rank, world, dev, instrum
     leg = Leg(world, dev)
 
     def step(i):
-        return trainer.step(*batches[i % 4], 1e-3)[1]
+        return trainer.step(*batches[i % 4], 1e-3)
 
     for i in range(warmup):
         step(i)
     warm_s = leg.run(step, 0, 0, warm_seconds)["warm_s"] if warm_seconds > 0 else 0.0
     graphs = None
     if os.environ.get("SAR_BENCH_GRAPH", "0") == "1" and world == 1:
+        # (a replay hands out no logits: the outputs of the last timed step exist on the eager path only)
+        assert not dump_dir, "--dump-outputs needs the eager step (SAR_BENCH_GRAPH=0)"
         # one captured hipGraph per resident batch: at bs = 32 the ~250 launches of a step are short enough for the
         # host launch path to show (experiment switch; the kernels read lr / step counters from device memory)
         graphs = []
@@ -506,6 +512,8 @@ def spectrogram_leg(args, steps, warmup, warm_seconds, rank, world, dev, instrum
             profiler.install(timer)
         res = leg.run(step, steps, 0, 0.0, trainer)
         profiler.install(None)
+        if dump_dir and rank == 0:
+            write_outputs(dump_dir, timed_outputs(res["last"], trainer.eng))
         if instrument_steps > 0:
             trainer.graph = False
             profiler.install(timer)
@@ -516,7 +524,7 @@ def spectrogram_leg(args, steps, warmup, warm_seconds, rank, world, dev, instrum
     else:
         res = leg.run(lambda i: graphs[i % 4].replay(), steps, 0, 0.0, None)
         res["last"] = step(0)
-    dt, loss = res["dt"], res["last"]
+    dt, loss = res["dt"], res["last"][1]
     out = None
     if rank == 0:
         summ = timer.summary()
@@ -605,6 +613,31 @@ def spectrogram_leg(args, steps, warmup, warm_seconds, rank, world, dev, instrum
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def timed_outputs(last, eng):
+    """what a caller of the timed train step holds after its LAST timed step, copied to the host before anything else runs: the
+    (logits, loss) the step returned and the engine's parameters and gradients it left behind"""
+    logits, loss = last
+    return {name: t.detach().float().cpu().numpy()
+            for name, t in (("logits", logits), ("loss", loss.reshape(1)), ("params", eng.flat), ("grads", eng.grad))}
+
+
+def write_outputs(ddir, arrays):
+    """--dump-outputs: DIR/<name>.npy in float32, at most DUMP_BUDGET_BYTES in all; an array over its share of the budget is
+    replaced by a fixed, seeded sample of its flattened elements (the same positions in every run)"""
+    import numpy as np
+    os.makedirs(ddir, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // len(arrays)      # (4 KiB per .npy header, generously)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(ddir, name + ".npy"), a)
+
+
 def strip_detail(leg, details, name):
     """the per-kernel tables of a leg leave the line (they were 1-2 KB per leg and pushed the legs' numbers out of the driver's tail):
     `--detail` prints them under `detail`, and every run writes them to gpurun_out/bench_detail.json when that directory exists"""
@@ -670,7 +703,12 @@ def main():
                          "measures ~4 %% low, profiles/r03_fp32_first_process.txt; the time really spent is reported as warm_s)")
     ap.add_argument("--cpu-sample", type=int, default=8,
                     help="clips in the CPU-baseline fallback batch (used only when a full --batch step does not fit the budget)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the selected workload, write what its LAST timed step computed -- logits, loss, "
+                         "the parameters and gradients it left -- as DIR/<name>.npy (float32, at most 64 MB in all; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
 
@@ -683,7 +721,8 @@ def main():
     details = {}
     if args.workload == "spectrogram":
         assert args.mfma in ("fp32", "f32_split", "f32_split_bf16x6"), "the spectrogram workload has no bf16 engine"
-        out = spectrogram_leg(args, args.steps, args.warmup, args.warm_seconds, rank, world, dev, mfma=args.mfma)
+        out = spectrogram_leg(args, args.steps, args.warmup, args.warm_seconds, rank, world, dev, mfma=args.mfma,
+                              dump_dir=args.dump_outputs)
         strip_detail(out, details, "headline")
         if rank == 0:
             out["box"] = dict(BOX)
@@ -744,7 +783,7 @@ def main():
                     sec[n] = strip_detail(r, details, n)
         sust = args.sustained_steps if args.steps < args.sustained_steps else 0
         head = stgcn_leg(args, args.mfma, args.steps, args.warmup, args.warm_seconds, rank, world, dev, not args.no_isolated_pass,
-                         stream=args.stream, sustained_steps=sust)
+                         stream=args.stream, sustained_steps=sust, dump_dir=args.dump_outputs)
         out = None
         if rank == 0:
             strip_detail(head, details, "headline")

@@ -79,3 +79,26 @@ def test_box_probe_reports_the_chip():
     assert 0.5 * 2500 < b["f16_mfma_tflops"] < 1.02 * 2500 and 0.5 * 2500 < b["bf16_mfma_tflops"] < 1.02 * 2500
     assert 1.0 < b["f16_mfma_clock_ghz"] <= 2.45 and 1.0 < b["f32_mfma_clock_ghz"] <= 2.45
     assert 3000 < b["copy_gbps"] < 8000 and b["probe_s"] < 4.0
+
+
+@pytest.mark.parametrize("workload", ["stgcn", "spectrogram"])
+def test_dump_outputs_writes_the_last_timed_step_and_repeats(workload, tmp_path):
+    """--dump-outputs DIR: the logits / loss / parameters / gradients of the LAST timed step as float32 .npy, at most 64 MB in all;
+    two runs with the same arguments see the same inputs, so (the train step being bitwise repeatable) they dump the same arrays."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        _, out = _run("--no-secondary", "--no-isolated-pass", "--workload", workload, "--dump-outputs", str(d))
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert files == ["grads.npy", "logits.npy", "loss.npy", "params.npy"], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f[:-4]: np.load(d / f) for f in files})
+        a = dumps[-1]
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+        assert a["logits"].shape == (4, 60) and a["loss"].shape == (1,)
+        assert a["params"].shape == a["grads"].shape and a["grads"].any()
+        assert abs(float(a["loss"][0]) - out["final_loss"]) < 1e-5      # the line's loss is the last timed step's
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name

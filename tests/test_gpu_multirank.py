@@ -106,11 +106,16 @@ def test_bench_starts_its_own_ranks(tmp_path):
 
 
 def test_bench_eight_ranks_rehearsal(tmp_path):
-    """the driver's 8-GPU command line rehearsed on ONE GPU -- `python bench.py --gpus 8 --quick --batch 2`
-    with all eight ranks on cuda:0 over gloo (SAR_BENCH_SHARE_GPU=1): the self-launch, the rendezvous port, the MAX-agreed warm-up
-    loop of Leg.run, per_rank_ms of length 8, every secondary leg at world 8, a clean exit.  (What it cannot rehearse is RCCL
-    over xGMI itself: tests/test_gpu_rccl.py runs the RCCL branches on a one-rank communicator.)"""
-    env = dict(os.environ, SAR_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    """the driver's 8-GPU command line -- `python bench.py --gpus 8 --quick --batch 2`, one rank per GPU:
+    the self-launch, the rendezvous port, the MAX-agreed warm-up loop of Leg.run, per_rank_ms of length 8, every secondary leg at
+    world 8, a clean exit.  It needs eight GPUs: eight ranks sharing one GPU (SAR_BENCH_SHARE_GPU=1) would hold more processes on
+    that device than a shared machine allows, so with fewer GPUs the test skips before it starts anything (tests/test_gpu_rccl.py
+    runs the RCCL branches on a one-rank communicator, test_bench_starts_its_own_ranks the self-launch at world 2)."""
+    found = torch.cuda.device_count()
+    if found < 8:
+        pytest.skip("needs 8 GPUs, found %d" % found)
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env.pop("SAR_BENCH_SHARE_GPU", None)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--quick", "--batch", "2", "--steps", "2",
