@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import stgcn as O
-from util import to_cn, from_cn, rel_err
+from util import to_cn, from_cn, rel_err, assert_bf16_close, bf as _bf, graph_ref as _graph_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +20,6 @@ pytestmark = pytest.mark.gpu
 def dev():
     assert torch.cuda.is_available()
     return torch.device("cuda:0")
-
-
-def _bf(t):
-    return t.float().bfloat16().double()
 
 
 def _A():
@@ -55,13 +51,6 @@ def _cn8(x, dev):
 def _back(x8, C, B, T):
     from sar_amd import ops8
     return from_cn(ops8.to_cn(x8, C).cpu(), B, T, 25)
-
-
-def assert_bf16_close(got, ref, what=""):
-    got, ref = got.double(), ref.double()
-    scale = ref.abs().max().item()
-    bad = (got - ref).abs() - (2.0 ** -8) * ref.abs() - 1e-5 * scale
-    assert bad.max().item() <= 0, "%s: worst excess %.3e (scale %.3e)" % (what, bad.max().item(), scale)
 
 
 def test_layout_roundtrip_and_padding(dev):
@@ -153,29 +142,6 @@ def test_temporal_conv_data_gradient(dev, B, f, T, s):
     part = pm[0].cpu().double().sum(dim=1)
     assert rel_err(part[:, 0], g_pre.sum(dim=(0, 2, 3))) < 1e-4
     assert rel_err(part[:, 1], (g_pre * (gx.double() - mean.double().view(1, -1, 1, 1))).sum(dim=(0, 2, 3))) < 1e-4
-
-
-def _graph_ref(x, kernel, bias, A, dev_tables):
-    """exact definition: z_k = bf16(fp32 gather of the bf16 src in table order), W rounded to bf16, float64 contraction"""
-    idx, wt = dev_tables.idx.cpu(), dev_tables.wt.cpu()                   # [3][V][4]
-    Bq, cin, T, V = x.shape
-    f = kernel.shape[3] // 3
-    xs = x.float()
-    out = torch.zeros(Bq, f, T, V, dtype=torch.float64)
-    Wk = _bf(kernel)[0, 0]                                                 # (cin, 3f)
-    for k in range(3):
-        z = torch.zeros(Bq, cin, T, V)
-        for w in range(V):
-            acc = None
-            for j in range(dev_tables.nz[k]):
-                term = wt[k, w, j] * xs[:, :, :, idx[k, w, j]]
-                acc = term if acc is None else torch.addcmul(acc, xs[:, :, :, idx[k, w, j]], wt[k, w, j])   # fp32 fma chain
-            z[:, :, :, w] = acc
-        zb = _bf(z)
-        out += torch.einsum("bctv,cm->bmtv", zb, Wk[:, k * f:(k + 1) * f])
-        if bias is not None:
-            out += bias.double()[k * f:(k + 1) * f].view(1, -1, 1, 1) * A[k].double().sum(dim=0).view(1, 1, 1, -1)
-    return out
 
 
 @pytest.mark.parametrize("B,cin,f,T", [(3, 3, 64, 13), (2, 64, 64, 10), (2, 64, 128, 7), (1, 128, 256, 5), (4, 256, 256, 3),
