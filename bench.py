@@ -2,13 +2,18 @@
 """bench.py -- ST-GCN training throughput on MI355X (BASELINE.json metric:
 "NTU-xsub clips/sec training (ST-GCN, bs=64/GPU)").
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full]          (N>1: launched by torch.distributed.run)
 
 A step = one full train step of the hot path on one synthetic batch resident in HBM: forward (data_bn,
 10 ST-GCN blocks, head), softmax-CE, backward of everything, gradient all-reduce (N>1), Nesterov SGD.
 Workload = BASELINE.json configs[1]: fp32, synthetic NTU-xsub clips (3,300,25,2), 60 classes, bs=64/GPU.
 Prints ONE JSON line on rank 0 (contract in the task statement) including
   roofline     -- the dominant kernel family (9x1 temporal-conv GEMMs), algorithmic FLOPs / HIP-event time
+A plain run measures the selected workload alone: set-up, W warm-up steps, --warm-seconds of untimed load, the K timed steps
+(the roofline comes from HIP events inside them), --dump-outputs, the line.  --full adds what takes runs of its own:
+  box          -- what this box sustains (sar_amd/box.py), the denominator of every roofline.frac_of_box
+  secondary    -- the other BASELINE configurations, each timed in this process before the headline
+  sustained    -- more timed steps behind the K; roofline.isolated -- 3 more steps with the weight-gradient stream off
   cpu_baseline -- the CPU oracle (torch CPU ops, "port") timed on this box's host cores on a bounded sample
 """
 import argparse
@@ -640,7 +645,8 @@ def write_outputs(ddir, arrays):
 
 def strip_detail(leg, details, name):
     """the per-kernel tables of a leg leave the line (they were 1-2 KB per leg and pushed the legs' numbers out of the driver's tail):
-    `--detail` prints them under `detail`, and every run writes them to gpurun_out/bench_detail.json when that directory exists"""
+    `--detail` prints them under `detail`, and a --full run also writes them to bench_detail.json in the output directory that
+    main() names, when that directory exists"""
     if leg is not None and "_detail" in leg:
         details[name] = leg.pop("_detail")
     return leg
@@ -677,32 +683,36 @@ def main():
                     help="fp32 = BASELINE.json configs[1] (default, the headline); bf16 = configs[2]: bf16 activations in HBM (CN8 "
                          "layout) + bf16 MFMA operands, fp32 accumulation / BatchNorm statistics / master weights; bf16_operands = "
                          "the round-1 intermediate (bf16 MFMA operands, fp32 activations in HBM)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the box probe, the secondary legs, the sustained steps, the "
+                         "isolated pass and the CPU baselines (the options below marked --full choose among them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-isolated-pass", action="store_true",
-                    help="skip the 3 extra untimed steps that measure the dominant kernel family with the side stream off "
+                    help="--full: skip the 3 extra untimed steps that measure the dominant kernel family with the side stream off "
                          "(profile runs: keeps the launch counts at warmup + steps)")
-    ap.add_argument("--no-secondary", action="store_true", help="headline line only (profile runs)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: no secondary legs")
     ap.add_argument("--secondary", default="f32_split,bf16,pathB,pathB_f32_split,pathB_pad250,pathB_pad250_f32_split,config5",
-                    help="comma list of the secondary legs run in the same process BEFORE the fp32 headline and reported under "
+                    help="--full: comma list of the secondary legs run in the same process BEFORE the fp32 headline and reported under "
                          "'secondary': f32_split = configs[1] with the GEMM contractions on the fp16 matrix pipe (fp32 storage and results), bf16 = configs[2] (sustained: >= 3 s of untimed load first), pathB = configs[3], pathB_pad250 = "
                          "configs[3] on the reference loader's real input (x250 up-sampling on the GPU), config5 = configs[4] (120 "
                          "classes, bone stream)")
     ap.add_argument("--detail", action="store_true",
                     help="print the per-kernel tables (kernel_ms_per_step, kernel_tflops, isolated) of every leg under 'detail' (default: "
-                         "they go to gpurun_out/bench_detail.json only, so that the line's tail holds every leg's numbers)")
-    ap.add_argument("--quick", action="store_true", help="tests: secondary legs of a few steps without warm-up seconds")
+                         "a --full run writes them to a file only, so that the line's tail holds every leg's numbers; see strip_detail)")
+    ap.add_argument("--quick", action="store_true", help="tests, --full: secondary legs of a few steps without warm-up seconds, "
+                                                         "a short box probe")
     ap.add_argument("--stream", default="joint", choices=["joint", "bone"],
                     help="input stream of the stgcn workload (bone = data_gen/gen_bone_data.py on the fly; config 5 = --classes 120 "
                          "--stream bone)")
     ap.add_argument("--sustained-steps", type=int, default=100,
-                    help="fp32 headline: after the K timed steps of the contract, time this many more with the same protocol and report "
-                         "them as 'sustained' (0 = off; skipped when K is already >= this)")
+                    help="--full, fp32 headline: after the K timed steps of the contract, time this many more with the same protocol "
+                         "and report them as 'sustained' (0 = off; skipped when K is already >= this)")
     ap.add_argument("--warm-seconds", type=float, default=3.0,
                     help="untimed load in front of the timed steps of the selected workload, in EVERY mode (with or without secondary "
                          "legs the headline is timed on a GPU that has been under its own load for this long: a cold first process "
                          "measures ~4 %% low, profiles/r03_fp32_first_process.txt; the time really spent is reported as warm_s)")
     ap.add_argument("--cpu-sample", type=int, default=8,
-                    help="clips in the CPU-baseline fallback batch (used only when a full --batch step does not fit the budget)")
+                    help="--full: clips in the CPU-baseline fallback batch (used only when a full --batch step does not fit the budget)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps of the selected workload, write what its LAST timed step computed -- logits, loss, "
                          "the parameters and gradients it left -- as DIR/<name>.npy (float32, at most 64 MB in all; rank 0)")
@@ -714,17 +724,18 @@ def main():
 
     import torch.distributed as dist
     rank, world, dev = rank_setup(args)
-    cpu_ok = rank == 0 and world == 1 and not args.no_cpu_baseline
-    # what this box sustains, measured before the first leg on every rank (rank 0's is reported): the denominators of frac_of_box
-    from sar_amd import box as box_probe
-    BOX.update(box_probe.measure(dev, quick=args.quick))
+    cpu_ok = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if args.full:
+        # what this box sustains, measured before the first leg on every rank (rank 0's is reported): the denominators of frac_of_box
+        from sar_amd import box as box_probe
+        BOX.update(box_probe.measure(dev, quick=args.quick))
     details = {}
     if args.workload == "spectrogram":
         assert args.mfma in ("fp32", "f32_split", "f32_split_bf16x6"), "the spectrogram workload has no bf16 engine"
         out = spectrogram_leg(args, args.steps, args.warmup, args.warm_seconds, rank, world, dev, mfma=args.mfma,
                               dump_dir=args.dump_outputs)
         strip_detail(out, details, "headline")
-        if rank == 0:
+        if rank == 0 and BOX:
             out["box"] = dict(BOX)
         if cpu_ok:
             out["cpu_baseline"] = cpu_baseline_spectrogram(2 if args.num_pad_frames else 4, num_pad_frames=args.num_pad_frames)
@@ -732,7 +743,8 @@ def main():
             out["summary"] = summary_of(out, None, world)
     else:
         sec, deferred = None, []
-        names = [] if args.no_secondary or args.mfma != "fp32" or args.stream != "joint" else [n for n in args.secondary.split(",") if n]
+        names = [] if not args.full or args.no_secondary or args.mfma != "fp32" or args.stream != "joint" else \
+            [n for n in args.secondary.split(",") if n]
         if names:
             # The other BASELINE configs in the same process, driver-timed with the headline.  bf16: the SUSTAINED rate (>= 3 s of
             # untimed load first) is `value`; the cold-GPU rate of a short run is first_run_value.  They run BEFORE the headline
@@ -781,9 +793,9 @@ def main():
                     raise SystemExit("unknown secondary leg %r" % n)
                 if rank == 0:
                     sec[n] = strip_detail(r, details, n)
-        sust = args.sustained_steps if args.steps < args.sustained_steps else 0
-        head = stgcn_leg(args, args.mfma, args.steps, args.warmup, args.warm_seconds, rank, world, dev, not args.no_isolated_pass,
-                         stream=args.stream, sustained_steps=sust, dump_dir=args.dump_outputs)
+        sust = args.sustained_steps if args.full and args.steps < args.sustained_steps else 0
+        head = stgcn_leg(args, args.mfma, args.steps, args.warmup, args.warm_seconds, rank, world, dev,
+                         args.full and not args.no_isolated_pass, stream=args.stream, sustained_steps=sust, dump_dir=args.dump_outputs)
         out = None
         if rank == 0:
             strip_detail(head, details, "headline")
@@ -793,7 +805,8 @@ def main():
                    "dtype": head["dtype"], "data": "synthetic", "config": head["config"], "roofline": head["roofline"]}
             if cpu_ok:
                 out["cpu_baseline"] = None      # (keeps its place in front of the long objects; filled below)
-            out["box"] = dict(BOX)
+            if BOX:
+                out["box"] = dict(BOX)
             out["legend"] = LEGEND
             out.update({k: v for k, v in head.items() if k not in out})
             if sec:
@@ -810,7 +823,7 @@ def main():
             out["detail"] = details
             out["summary"] = out.pop("summary")                  # ... also with the tables in the line
         ddir = os.path.join(ROOT, "gpurun_out")
-        if os.path.isdir(ddir) and os.access(ddir, os.W_OK) and world == 1:
+        if args.full and os.path.isdir(ddir) and os.access(ddir, os.W_OK) and world == 1:
             try:
                 with open(os.path.join(ddir, "bench_detail.json"), "w") as f:
                     json.dump({"args": vars(args), "box": dict(BOX), "detail": details}, f)

@@ -1,7 +1,8 @@
 """The shape of bench.py's JSON line: the driver keeps the TAIL of the output and cuts strings at 120
-characters, so (i) the last key is a compact `summary` of every leg and of the box calibration, under 1 KB at one rank; (ii) no
-prose field of a leg is longer than 120 characters; (iii) the per-kernel tables stay out of the default line (`--detail`);
-(iv) the `box` probe (csrc/box_probe.hip through the C ABI) reports plausible figures of the chip."""
+characters, so under --full (i) the last key is a compact `summary` of every leg and of the box calibration, under 1 KB at one rank;
+(ii) no prose field of a leg is longer than 120 characters; (iii) the per-kernel tables stay out of the default line (`--detail`);
+(iv) the `box` probe (csrc/box_probe.hip through the C ABI) reports plausible figures of the chip.  A plain run (no --full) times
+the headline and measures nothing else."""
 import json
 import os
 import subprocess
@@ -38,7 +39,7 @@ def _run(*extra):
 
 
 def test_default_line_ends_with_a_compact_summary_of_every_leg():
-    line, out = _run()
+    line, out = _run("--full")
     assert list(out)[-1] == "summary"
     tail = json.dumps(out["summary"])
     assert len(tail) < 1024 and line.rstrip().endswith(tail + "}")
@@ -61,8 +62,27 @@ def test_default_line_ends_with_a_compact_summary_of_every_leg():
     assert len(line) < 16384
 
 
+def test_plain_line_times_the_headline_alone():
+    """without --full: no box probe, secondary leg, sustained steps, isolated pass or CPU baseline -- only the headline's timed
+    steps and the roofline taken from HIP events inside them"""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4",
+                        "--warm-seconds", "0"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["metric"] == "NTU-xsub clips/sec training (ST-GCN, bs=64/GPU)" and out["unit"] == "clips/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 2 and out["warmup"] == 1
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 4e3 / out["ms_per_step"]) < 1e-3 * out["value"]
+    for k in ("box", "secondary", "sustained", "cpu_baseline", "first_run_value"):
+        assert k not in out, k
+    assert out["roofline"]["launches"] > 0 and "isolated" not in out["roofline"] and "frac_of_box" not in out["roofline"]
+    assert list(out)[-1] == "summary" and set(out["summary"]["legs"]) == {"fp32"}
+
+
 def test_detail_flag_prints_the_kernel_tables():
-    line, out = _run("--detail", "--secondary", "f32_split")
+    line, out = _run("--full", "--detail", "--secondary", "f32_split")
     assert list(out)[-1] == "summary"
     d = out["detail"]
     assert d["headline"]["kernel_ms_per_step"] and d["f32_split"]["kernel_ms_per_step"]

@@ -90,7 +90,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     env = dict(os.environ, SAR_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--full",
                         "--no-cpu-baseline", "--secondary", "bf16,pathB", "--sustained-steps", "0"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -118,7 +118,7 @@ def test_bench_eight_ranks_rehearsal(tmp_path):
     env.pop("SAR_BENCH_SHARE_GPU", None)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--quick", "--batch", "2", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--full", "--quick", "--batch", "2", "--steps", "2",
                         "--warmup", "1", "--no-cpu-baseline", "--sustained-steps", "0", "--warm-seconds", "0"],
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

@@ -71,7 +71,7 @@ def test_bench_reports_the_live_rccl_communicator(tmp_path):
     """bench.py --gpus 1 under SAR_FORCE_DDP=1: rank set-up on nccl, the timed steps go through the bucketed exchange, and the
     line says so (rccl_ranks / dist_backend from the live communicator, the collective's time, the bucket count)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
-                        "--no-cpu-baseline", "--secondary", "bf16,pathB", "--quick"], env=_env(), capture_output=True, text=True,
+                        "--no-cpu-baseline", "--full", "--secondary", "bf16,pathB", "--quick"], env=_env(), capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

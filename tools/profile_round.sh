@@ -19,6 +19,6 @@ rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d $O/clock -
 if [ -n "$SAR_VALU_PASS" ]; then
   rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d $O/valu -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-isolated-pass --no-secondary --warm-seconds 0 --sustained-steps 0 "$@" > $O/bench_under_valu.log 2>&1
 fi
-cd $R && python3 bench.py --steps 10 --warmup 3 --no-secondary "$@" > $O/bench_plain.log 2>&1
+cd $R && python3 bench.py --full --steps 10 --warmup 3 --no-secondary "$@" > $O/bench_plain.log 2>&1
 tail -1 $O/bench_plain.log | cut -c1-400
 ls $O/*/*/ | head -20
