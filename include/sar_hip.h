@@ -635,6 +635,51 @@ int sar_graph_gather_expand_f32(const float* in, int64_t ld_in, const int32_t* i
                                 int F, int V, int64_t n, float* out, int64_t ld_out, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * ProjectionGraphConv(64, 32) of ST-PGCN (models/stpgcn.py:11-47 with GraphConv models/gcn.py:22-37; the layer between block 0
+ * and block 1, models/stpgcn.py:141-152), fp32.  x: block 0's output, CN layout [64][ld >= B*P] with column b*P + p, P = T*V.
+ * Parameters in Keras layouts: centers, variance [64][32] (shape (1, 64, 1, 32)), W [64][64] (Conv1D kernel (1, 64, 64)),
+ * bias [64]; s = sigmoid(variance).  q is [32][B*P] (row j = vertex j; ld = B*P).  Every column sum is a per-workgroup
+ * partial (nparts = sar_pgc_nparts(P) per sample, a function of P alone) reduced in a fixed order: no atomics.
+ *   sar_pgc_assign_f32      q = softmax_j(-0.5 max(sum_c ((x - centers) / s)^2, 1e-12))  -- models/stpgcn.py:30-34; part
+ *                           [B][nparts][SAR_PGC_FWD_PART] = partials of (x q^T [64][32], sum_p q [32])
+ *   sar_pgc_small_fwd_f32   one workgroup per sample: zp = (x q^T - centers qs) / (s qs), zn = l2_normalize_j(zp), A = zn^T zn,
+ *                           g = W^T zn + bias, h = g A  -- models/stpgcn.py:36-41, models/gcn.py:34-36; saved [B][SAR_PGC_SAVED] =
+ *                           S | zp | zn | g | h ([64][32] each) | A [32][32] | qs [32] | sum_j zp^2 [64]
+ *   sar_pgc_project_f32     out = x + (q h^T)^T  -- models/stpgcn.py:42-46 (out may not alias x)
+ *   sar_pgc_bwd_reduce_f32  part [B][nparts][SAR_PGC_DH_PART] = partials of dh = dout q^T
+ *   sar_pgc_small_bwd_f32   per sample: dsaved [B][SAR_PGC_DSAVED] = dS = dzp / (s qs) [64][32] | dqs [32]; slab [B][SAR_PGC_SLAB] =
+ *                           dW [64][64] | dbias [64] | -dzp / s [64][32] | -dzp zp / s [64][32]  (sum over B: sar_slab_reduce_f32)
+ *   sar_pgc_bwd_column_f32  dx = dout + dS q^T - sum_j dl (x - centers) / s^2 with dl the softmax backward of dq = dout^T h + x^T dS
+ *                           + dqs (0 where the 1e-12 clamp holds); part [B][nparts][SAR_PGC_BWD_PART] = partials of sum_p dl z |
+ *                           sum_p dl z^2, z = (x - centers) / s
+ *   sar_pgc_param_grad_f32  from colsum (the column partials summed) and pooled (the slabs' last 4096 floats summed):
+ *                           dcenters = pooled + colsum / s, ds likewise, dvariance = ds s (1 - s)
+ * ------------------------------------------------------------------------------------------------ */
+#define SAR_PGC_C 64
+#define SAR_PGC_J 32
+#define SAR_PGC_FWD_PART 2080
+#define SAR_PGC_DH_PART 2048
+#define SAR_PGC_BWD_PART 4096
+#define SAR_PGC_SAVED 11360
+#define SAR_PGC_DSAVED 2080
+#define SAR_PGC_SLAB 8256
+int sar_pgc_nparts(int64_t P);
+int sar_pgc_assign_f32(const float* x, int64_t ld_x, int B, int64_t P, const float* centers, const float* variance, float* q,
+                       float* part, sar_stream_t s);
+int sar_pgc_small_fwd_f32(const float* part, int B, int nparts, const float* centers, const float* variance, const float* W,
+                          const float* bias, float* saved, sar_stream_t s);
+int sar_pgc_project_f32(const float* x, int64_t ld_x, const float* q, const float* saved, int B, int64_t P, float* out, int64_t ld_out,
+                        sar_stream_t s);
+int sar_pgc_bwd_reduce_f32(const float* dout, int64_t ld_dout, const float* q, int B, int64_t P, float* part, sar_stream_t s);
+int sar_pgc_small_bwd_f32(const float* part, int B, int nparts, const float* variance, const float* W, const float* saved,
+                          float* dsaved, float* slab, sar_stream_t s);
+int sar_pgc_bwd_column_f32(const float* x, int64_t ld_x, const float* dout, int64_t ld_dout, const float* q, const float* saved,
+                           const float* dsaved, const float* centers, const float* variance, int B, int64_t P, float* dx,
+                           int64_t ld_dx, float* part, sar_stream_t s);
+int sar_pgc_param_grad_f32(const float* colsum, const float* pooled, const float* variance, float* dcenters, float* dvariance,
+                           sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 configuration (bf16 activations in HBM, bf16 MFMA operands, fp32 accumulation, fp32
  * BatchNorm statistics, fp32 master weights).
  *

@@ -165,6 +165,15 @@ SIGNATURES = {
     "sar_gin_bwd_reduce_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _fp, _fp, _i, _i, _i64, _fp, _fp]),
     "sar_gin_bwd_apply_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, _i, _i, _i64, _fp, _i64, _fp]),
     "sar_gin_eps_grad_f32": (_i, [_fp, _fp, _i64, _fp, _fp, _fp]),
+    # ST-PGCN projection graph convolution (csrc/pgc.hip)
+    "sar_pgc_nparts": (_i, [_i64]),
+    "sar_pgc_assign_f32": (_i, [_fp, _i64, _i, _i64, _fp, _fp, _fp, _fp, _fp]),
+    "sar_pgc_small_fwd_f32": (_i, [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "sar_pgc_project_f32": (_i, [_fp, _i64, _fp, _fp, _i, _i64, _fp, _i64, _fp]),
+    "sar_pgc_bwd_reduce_f32": (_i, [_fp, _i64, _fp, _i, _i64, _fp, _fp]),
+    "sar_pgc_small_bwd_f32": (_i, [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "sar_pgc_bwd_column_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, _i, _i64, _fp, _i64, _fp, _fp]),
+    "sar_pgc_param_grad_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp]),
     "sar_graph_dense_nparts": (_i, [_i64]),
     "sar_graph_dense_fwd_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _i64, _fp, _fp, _i64, _fp]),
     "sar_graph_dense_bwd_data_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _i64, _fp]),

@@ -779,6 +779,61 @@ def gin_eps_grad(G, W, eps, deps):
     check(L.load().sar_gin_eps_grad_f32(ptr(G), ptr(W), G.numel(), ptr(eps), ptr(deps), stream_ptr()), "sar_gin_eps_grad_f32")
 
 
+# ------------------------------------------------------------------------------------------------ ST-PGCN projection graph convolution
+# csrc/pgc.hip (include/sar_hip.h: ProjectionGraphConv).  x / out / dout / dx: CN [64][B*P]; q: [32][B*P]
+PGC_C, PGC_J = 64, 32
+PGC_FWD_PART, PGC_DH_PART, PGC_BWD_PART, PGC_SAVED, PGC_DSAVED, PGC_SLAB = 2080, 2048, 4096, 11360, 2080, 8256
+
+
+def _pgc_args(x, B, P):
+    assert x.dtype == torch.float32 and x.is_cuda and x.shape[0] == PGC_C and x.stride(1) == 1 and x.shape[1] == B * P
+    return x.stride(0)
+
+
+def pgc_forward(x, B, P, centers, variance, W, bias, out):
+    """out = x + the projection graph convolution of x (models/stpgcn.py:23-47).  Returns (q [32][B*P], saved [B][PGC_SAVED]):
+    what the backward pass needs (saved: S | zp | zn | g | h | A | qs | sum_j zp^2 per sample)."""
+    lib, dev = L.load(), x.device
+    ld = _pgc_args(x, B, P)
+    G = lib.sar_pgc_nparts(P)
+    q = torch.empty((PGC_J, B * P), dtype=torch.float32, device=dev)
+    part = torch.empty((B, G, PGC_FWD_PART), dtype=torch.float32, device=dev)
+    saved = torch.empty((B, PGC_SAVED), dtype=torch.float32, device=dev)
+    check(lib.sar_pgc_assign_f32(ptr(x), ld, B, P, ptr(_f32(centers)), ptr(_f32(variance)), ptr(q), ptr(part), stream_ptr()),
+          "sar_pgc_assign_f32")
+    check(lib.sar_pgc_small_fwd_f32(ptr(part), B, G, ptr(centers), ptr(variance), ptr(_f32(W)), ptr(_f32(bias)), ptr(saved),
+                                    stream_ptr()), "sar_pgc_small_fwd_f32")
+    check(lib.sar_pgc_project_f32(ptr(x), ld, ptr(q), ptr(saved), B, P, ptr(out), _pgc_args(out, B, P), stream_ptr()),
+          "sar_pgc_project_f32")
+    return q, saved
+
+
+def pgc_backward(x, dout, q, saved, B, P, centers, variance, W, dx, g_centers, g_variance, g_kernel_bias):
+    """dx = the gradient w.r.t. x; g_centers / g_variance ([64][32]) and g_kernel_bias (the Conv1D kernel [64*64] followed by its
+    bias [64], one contiguous range) are written, not accumulated.  Every sum runs in a fixed order."""
+    lib, dev = L.load(), x.device
+    ld = _pgc_args(x, B, P)
+    G = lib.sar_pgc_nparts(P)
+    assert g_kernel_bias.is_contiguous() and g_kernel_bias.numel() == PGC_C * PGC_C + PGC_C
+    part = torch.empty((B, G, PGC_DH_PART), dtype=torch.float32, device=dev)
+    check(lib.sar_pgc_bwd_reduce_f32(ptr(dout), _pgc_args(dout, B, P), ptr(q), B, P, ptr(part), stream_ptr()), "sar_pgc_bwd_reduce_f32")
+    dsaved = torch.empty((B, PGC_DSAVED), dtype=torch.float32, device=dev)
+    slab = torch.empty((B, PGC_SLAB), dtype=torch.float32, device=dev)
+    check(lib.sar_pgc_small_bwd_f32(ptr(part), B, G, ptr(_f32(variance)), ptr(_f32(W)), ptr(saved), ptr(dsaved), ptr(slab), stream_ptr()),
+          "sar_pgc_small_bwd_f32")
+    cpart = torch.empty((B, G, PGC_BWD_PART), dtype=torch.float32, device=dev)
+    check(lib.sar_pgc_bwd_column_f32(ptr(x), ld, ptr(dout), dout.stride(0), ptr(q), ptr(saved), ptr(dsaved), ptr(_f32(centers)),
+                                     ptr(variance), B, P, ptr(dx), _pgc_args(dx, B, P), ptr(cpart), stream_ptr()), "sar_pgc_bwd_column_f32")
+    nwb = PGC_C * PGC_C + PGC_C
+    sums = torch.empty(2 * PGC_BWD_PART, dtype=torch.float32, device=dev)      # column partials | pooled slabs
+    check(lib.sar_slab_reduce_f32(ptr(slab), B, PGC_SLAB, nwb, ptr(g_kernel_bias), stream_ptr()), "sar_slab_reduce_f32")
+    check(lib.sar_slab_reduce_f32(ptr(slab) + 4 * nwb, B, PGC_SLAB, PGC_BWD_PART, ptr(sums) + 4 * PGC_BWD_PART, stream_ptr()),
+          "sar_slab_reduce_f32")
+    check(lib.sar_slab_reduce_f32(ptr(cpart), B * G, PGC_BWD_PART, PGC_BWD_PART, ptr(sums), stream_ptr()), "sar_slab_reduce_f32")
+    check(lib.sar_pgc_param_grad_f32(ptr(sums), ptr(sums) + 4 * PGC_BWD_PART, ptr(variance), ptr(_f32(g_centers)), ptr(_f32(g_variance)),
+                                     stream_ptr()), "sar_pgc_param_grad_f32")
+
+
 # ------------------------------------------------------------------------------------------------ ResNet-18 ops
 def _shape_tag(geo):
     """SAR_PROFILE_SHAPES=1 (diagnostic, tools/pathb_layers.py): one profiler bucket per layer geometry"""

@@ -145,6 +145,7 @@ class STGCN:
             if kind == "conv":
                 self._add(pre + "res.kernel", (1, 1, cin, f)), self._add(pre + "res.bias", (f,))
                 self._add(pre + "res_bn.gamma", (f,)), self._add(pre + "res_bn.beta", (f,))
+            self._params_after_block(i)
             cin = f
         self.C_last = cin
         self._add("logits.kernel", (1, 1, cin, num_classes)), self._add("logits.bias", (num_classes,))
@@ -337,6 +338,22 @@ class STGCN:
             torch.cuda.current_stream().wait_stream(self._side)      # every weight gradient is in self.grad
         self._saved = None
 
+    # ------------------------------------------------------------------ a layer between two blocks (sar_amd/stpgcn.py)
+    # Hook points of a sibling model that inserts a layer after block i: its parameters follow block i's in the flat buffer, its
+    # forward runs on block i's output, its backward on the gradient that block i + 1 hands down.  No-ops here.
+    def _params_after_block(self, i):
+        pass
+
+    def _layer_after(self, i):
+        """does a layer sit between block i and block i + 1?"""
+        return False
+
+    def _after_block_forward(self, i, h, B, T, training, saved, keep):
+        return h
+
+    def _after_block_backward(self, i, dY, B):
+        return dY
+
     # ------------------------------------------------------------------ parameters
     def _add(self, name, shape):
         self.shapes[name] = tuple(shape)
@@ -352,7 +369,7 @@ class STGCN:
             if k == "adjacency_matrix":
                 self.p[k].copy_(torch.from_numpy(self.A_host))
             elif k.endswith(".kernel"):
-                fan_out = shp[0] * shp[1] * shp[3]
+                fan_out = int(np.prod(shp[:-2])) * shp[-1]      # (kh, kw, in, out) and Conv1D (k, in, out)
                 std = math.sqrt(2.0 / fan_out) / .87962566103423978
                 w = torch.empty(shp, dtype=torch.float64)
                 torch.nn.init.trunc_normal_(w, 0.0, std, -2 * std, 2 * std, generator=gen)
@@ -444,6 +461,7 @@ class STGCN:
         Tc, cin = T, Cin
         for i, (f, s, res) in enumerate(self.blocks):
             h, Tc = self._block_forward(i, h, cin, f, s, B, Tc, training, saved, keep)
+            h = self._after_block_forward(i, h, B, Tc, training, saved, keep)
             cin = f
         # ---- head (models/stgcn.py:153-158)
         feat = torch.empty((N, cin), dtype=torch.float32, device=dev)
@@ -636,10 +654,13 @@ class STGCN:
         fuse = self._fuse_tail_f32()
         gated = None
         for i in reversed(range(len(self.blocks))):
+            dY = self._after_block_backward(i, dY, B)
             if fuse:
                 sbb = sv["blocks"][i - 1] if i >= 1 else None
+                # (a layer between the blocks adds its own gradient first: no gating of block i - 1 inside block i's data gradient)
                 below = sbb if (sbb is not None and self.kinds[i - 1] != "conv" and sbb.get("ymask") is not None
-                                and sv["blocks"][i]["kind"] != "none" and sv["blocks"][i]["cin"] % 8 == 0) else None
+                                and sv["blocks"][i]["kind"] != "none" and sv["blocks"][i]["cin"] % 8 == 0
+                                and not self._layer_after(i - 1)) else None
                 dY, gated = self._block_backward(i, sv["blocks"][i], dY, B, gated, below)
             else:
                 dY = self._block_backward(i, sv["blocks"][i], dY, B)
