@@ -597,6 +597,27 @@ int sar_graph_dense_dadj_f32(const float* y, int64_t ld_y, const float* dout, in
                            int64_t nframes, int nsplit, float* slab, float* dA, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dense adjacency that depends on the FRAME (models/stgcn_debug.py SGTACN: einsum 'nkctv,ktvw->nctw', one trainable table per
+ * block): At is [K][T][V][V] contiguous (the Keras variable's layout), activations fp32 CN with column (b*T + t)*V + v, so B and
+ * T are passed separately.  csrc/graph_dense_t.hip (fp32 MFMA): K <= 4, V <= 32, K*V <= 76.
+ *   fwd       out[m, (b,t,w)]      = sum_k sum_v y[k*F + m, (b,t,v)] * At[k, t, v, w]   (+ add[m, ..] when add != NULL;
+ *                                    + partials[F][nparts][2] = (sum, sum of squares) per row and part when partials != NULL,
+ *                                    nparts = sar_graph_dense_t_nparts(B, T))
+ *   bwd_data  dy[k*F + m, (b,t,v)] = sum_w dout[m, (b,t,w)] * At[k, t, v, w]
+ *   dadj      dAt[k, t, v, w]      = sum_{m, b} y[k*F + m, (b,t,v)] * dout[m, (b,t,w)]   (slab: scratch of
+ *                                    sar_graph_dense_t_dadj_slab_floats floats; sample ranges are summed in a fixed order)
+ * out / dy of a sample do not depend on the other samples of the batch; no atomics, repeated launches are bitwise equal.
+ * ------------------------------------------------------------------------------------------------ */
+int sar_graph_dense_t_nparts(int B, int T);
+int sar_graph_dense_t_fwd_f32(const float* y, int64_t ld_y, const float* At, float* out, int64_t ld_out, int K, int F, int V,
+                              int B, int T, float* partials, const float* add, int64_t ld_add, sar_stream_t s);
+int sar_graph_dense_t_bwd_data_f32(const float* dout, int64_t ld_dout, const float* At, float* dy, int64_t ld_dy, int K, int F,
+                                   int V, int B, int T, sar_stream_t s);
+int64_t sar_graph_dense_t_dadj_slab_floats(int K, int V, int B, int T);
+int sar_graph_dense_t_dadj_f32(const float* y, int64_t ld_y, const float* dout, int64_t ld_dout, int K, int F, int V, int B,
+                               int T, float* slab, float* dAt, sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * Graph isomorphism convolution, SURVEY.md 8(f)-4 (models/gcn.py:112-163 GraphIsoConvTD as used by models/stgin.py:24-25):
  * fp32 CN layout; the K branch MLPs of a layer are stacked along the channel axis (row k*C + c).
  *   sar_gin_adjacency_f32   table[k][a][b] = A[k][b][a] (k < Km1), table[Km1] = (1 + eps[0]) I  -- models/gcn.py:150-153

@@ -708,6 +708,37 @@ def graph_dense_dA(y, dout, dA, K, F, V, nframes, nsplit=64):
                                      ptr(slab), ptr(_f32(dA)), stream_ptr()), "sar_graph_dense_dadj_f32")
 
 
+# ------------------------------------------------------------------------------------------------ dense adjacency per frame
+def graph_dense_t_fwd(y, At, out, K, F, V, B, T, stats=False, add=None):
+    """out[m, (b,t,:)] = sum_k y[k F + m, (b,t,:)] . At[k, t] (+ add[m]) (sar_graph_dense_t_fwd_f32); At (K, T, V, V) contiguous;
+    returns (partials, nparts) when stats."""
+    lib = L.load()
+    assert At.is_contiguous() and tuple(At.shape) == (K, T, V, V), "At must be a contiguous (K, T, V, V) table"
+    partials, nparts = None, 0
+    if stats:
+        nparts = lib.sar_graph_dense_t_nparts(B, T)
+        partials = torch.empty((F, nparts, 2), dtype=torch.float32, device=y.device)
+    check(lib.sar_graph_dense_t_fwd_f32(ptr(_f32(y)), y.stride(0), ptr(_f32(At)), ptr(_f32(out)), out.stride(0), K, F, V, B, T,
+                                        ptr(partials), ptr(_f32(add)), add.stride(0) if add is not None else 0, stream_ptr()),
+          "sar_graph_dense_t_fwd_f32")
+    return (partials, nparts) if stats else None
+
+
+def graph_dense_t_bwd_data(dout, At, dy, K, F, V, B, T):
+    assert At.is_contiguous() and tuple(At.shape) == (K, T, V, V), "At must be a contiguous (K, T, V, V) table"
+    check(L.load().sar_graph_dense_t_bwd_data_f32(ptr(_f32(dout)), dout.stride(0), ptr(_f32(At)), ptr(_f32(dy)), dy.stride(0), K, F, V,
+                                                  B, T, stream_ptr()), "sar_graph_dense_t_bwd_data_f32")
+
+
+def graph_dense_t_dA(y, dout, dAt, K, F, V, B, T):
+    """dAt (K, T, V, V) contiguous = sum over channels and samples of y (x) dout per frame (sar_graph_dense_t_dadj_f32)"""
+    lib = L.load()
+    assert dAt.is_contiguous() and dAt.numel() == K * T * V * V
+    slab = torch.empty(lib.sar_graph_dense_t_dadj_slab_floats(K, V, B, T), dtype=torch.float32, device=y.device)
+    check(lib.sar_graph_dense_t_dadj_f32(ptr(_f32(y)), y.stride(0), ptr(_f32(dout)), dout.stride(0), K, F, V, B, T, ptr(slab),
+                                         ptr(_f32(dAt)), stream_ptr()), "sar_graph_dense_t_dadj_f32")
+
+
 # ------------------------------------------------------------------------------------------------ graph isomorphism conv
 def conv_gemm_nparts(B, V, T_src, T_out, Kc, M, taps=1, stride=1, pad=0, transposed=False, epi=L.SAR_EPI_STATS):
     """partial sums per output row that sar_conv_gemm_f32 (TEMPORAL) writes for this geometry"""

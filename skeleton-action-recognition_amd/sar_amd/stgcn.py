@@ -149,7 +149,7 @@ class STGCN:
             cin = f
         self.C_last = cin
         self._add("logits.kernel", (1, 1, cin, num_classes)), self._add("logits.bias", (num_classes,))
-        if self.dense_A:
+        if self.dense_A and self._shared_adjacency():
             self._add("adjacency_matrix", (KS, num_node, num_node))
         # flat storage: every offset is a multiple of 4 floats so that each weight view is 16-byte aligned
         # (the GEMM kernels stage weight rows as float4); a bias stays glued to its kernel because the
@@ -256,7 +256,7 @@ class STGCN:
             self._wT_perm, self._wT = pb, torch.zeros(off, dtype=torch.float32, device=dev)
         self.p = {k: self._view(self.flat, k) for k in self.shapes}
         self.g = {k: self._view(self.grad, k) for k in self.shapes}
-        if self.dense_A:
+        if "adjacency_matrix" in self.p:
             self.A = self.p["adjacency_matrix"]          # the trainable copy (initialised from the graph in _init_params)
         self.bn = {"data_bn": _BN(nch, dev)}
         for i, (f, s, res) in enumerate(self.blocks):
@@ -353,6 +353,33 @@ class STGCN:
 
     def _after_block_backward(self, i, dY, B):
         return dY
+
+    # ------------------------------------------------------------------ the dense contraction of a block (sar_amd/stgcn_ta.py)
+    # Hook points of a sibling model whose blocks contract with tables of their own: which table block i uses and which three ops
+    # (csrc/graph_dense.hip here: ONE (K, V, V) adjacency shared by the blocks, its gradient summed over them at the end of backward).
+    def _shared_adjacency(self):
+        """is the trainable adjacency the single parameter `adjacency_matrix` shared by all blocks?"""
+        return True
+
+    def _dense_fwd(self, i, y3, g, f, B, T, training):
+        return ops.graph_dense_fwd(y3, self.A, g, KS, f, self.V, B * T, stats=training)
+
+    def _dense_bwd_data(self, i, dg, dy3, f, B, T):
+        ops.graph_dense_bwd_data(dg, self.A, dy3, KS, f, self.V, B * T)
+
+    def _dense_dA(self, i, y3, dg, f, B, T):
+        """one V x V x K block per layer; summed over the layers by _dense_backward_end"""
+        ops.graph_dense_dA(y3, dg, self._dA_layers[i], KS, f, self.V, B * T)
+
+    def _dense_backward_begin(self, dev):
+        self._dA_layers = torch.zeros((len(self.blocks), KS * self.V * self.V), dtype=torch.float32, device=dev)
+
+    def _dense_backward_end(self):
+        """the adjacency is shared by all blocks: dA = sum over the layers (fixed order); zero while frozen"""
+        n = KS * self.V * self.V
+        ops.check(L.load().sar_slab_reduce_f32(ops.ptr(self._dA_layers), len(self.blocks), n, n,
+                                               ops.ptr(self.g["adjacency_matrix"]), ops.stream_ptr()), "sar_slab_reduce_f32")
+        self._dA_layers = None
 
     # ------------------------------------------------------------------ parameters
     def _add(self, name, shape):
@@ -488,7 +515,7 @@ class STGCN:
             y3 = torch.empty((KS * f, n_in), dtype=torch.float32, device=dev)
             ops.conv_gemm(L.SAR_CONV_TEMPORAL, X, y3, self.p[pre + "gcn.kernel"], 0, KS * f, B=B, V=V, T_src=T, T_out=T, Kc=cin,
                           M=KS * f, taps=1, stride=1, pad=0, bias=self.p[pre + "gcn.bias"])
-            r1 = ops.graph_dense_fwd(y3, self.A, g, KS, f, V, B * T, stats=training)
+            r1 = self._dense_fwd(i, y3, g, f, B, T, training)
         else:
             gimg = self._simg(pre + "gcn.f") if training else None
             if gimg is not None or (training and self._cell_live(pre + "gcn.f", "gfwd", "gwgrad")):
@@ -646,7 +673,7 @@ class STGCN:
         dY = torch.empty(sv["y_last_shape"], dtype=torch.float32, device=dev)
         ops.pool_bwd(dfeat, B, sv["T_last"] * V, M, dY)
         if self.dense_A:
-            self._dA_layers = torch.zeros((len(self.blocks), KS * V * V), dtype=torch.float32, device=dev)
+            self._dense_backward_begin(dev)
         # fp32 engine, gather tables: the graph data gradient of block i gates the output gradient of block i - 1 with that block's
         # ReLU mask and reduces its BatchNorm-backward sums in the same epilogue (SAR_EPI_ADD_GATE; sar_amd/stgcn8.py does the same
         # for the bf16 engine) -- the bn_add_relu_bwd_reduce pass and the masked-gradient write of the apply pass are gone for
@@ -667,11 +694,8 @@ class STGCN:
             if self._deferred:
                 self._flush_deferred()
             self._buckets_after_block(i, bucket_cb)
-        if self.dense_A:       # the adjacency is shared by all blocks: dA = sum over the layers (fixed order); zero while frozen
-            n = KS * V * V
-            ops.check(L.load().sar_slab_reduce_f32(ops.ptr(self._dA_layers), len(self.blocks), n, n,
-                                                   ops.ptr(self.g["adjacency_matrix"]), ops.stream_ptr()), "sar_slab_reduce_f32")
-            self._dA_layers = None
+        if self.dense_A:
+            self._dense_backward_end()
         # data_bn gamma/beta (the input needs no gradient)
         x = sv["x"]
         nch = V * self.C_in
@@ -842,9 +866,9 @@ class STGCN:
         X, y3, T, cin, f, kind = sb["X"], sb["y3"], sb["T"], sb["cin"], sb["f"], sb["kind"]
         n_in = B * T * V
         dy3 = torch.empty_like(y3)
-        ops.graph_dense_bwd_data(dg, self.A, dy3, KS, f, V, B * T)
-        if self.train_adjacency:       # one V x V x K block per layer; summed over the layers at the end of backward()
-            ops.graph_dense_dA(y3, dg, self._dA_layers[i], KS, f, V, B * T)
+        self._dense_bwd_data(i, dg, dy3, f, B, T)
+        if self.train_adjacency:
+            self._dense_dA(i, y3, dg, f, B, T)
         self._off_critical_path(lambda: ops.conv_wgrad(
             L.SAR_CONV_TEMPORAL, X, dy3, flat_g, B=B, V=V, T_src=T, T_out=T, Kc=cin, M=KS * f, taps=1, stride=1, pad=0,
             w_stride_tap=0, w_stride_c=KS * f, wsize=cin * KS * f, bsize=KS * f, slabs=self._slabs), X, dy3)
