@@ -767,6 +767,19 @@ int sar_cn_to_cn8(const float* x, int64_t ld_x, void* out, int64_t ld_out, int C
 int sar_cn8_to_cn(const void* x, int64_t ld_x, float* out, int64_t ld_out, int C, int64_t n, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pre-normalisation of raw skeleton clips, data_gen/preprocess.py:8-88 `pre_normalization(data, zaxis, xaxis)` with
+ * data_gen/rotation.py:5-42 (csrc/prenorm.hip).  x, out: (N, 3, T, V, M) fp32, C-contiguous, NOT overlapping (frames are
+ * gathered).  Per clip: pad the null frames of every non-null body by looping the clip (preprocess.py:13-32), subtract body 0's
+ * joint 1 from every non-null joint (:37-45; joint 1 is hard-coded there), rotate body 0's frame-0 bone z0 -> z1 onto z (:50-65)
+ * and then x1 -> x0 onto x (:70-85).  The matrices are computed and applied in float64 from fp32 joints, each rotation rounded
+ * to fp32, as in the reference; both identity branches of rotation.py:10 / :38 are kept (an antiparallel bone is not turned).
+ * Null = all coordinates exactly zero (the reference tests sum() == 0).  One workgroup per clip, no atomics, no workspace.
+ * Built for 2 <= V <= 32, M <= 4, T <= 2048 (SAR_E_UNSUP otherwise); joint indices outside [0, V) or overlapping buffers:
+ * SAR_E_ARG.  Nothing is launched on an error.
+ * ------------------------------------------------------------------------------------------------ */
+int sar_pre_normalize_f32(const float* x, float* out, int N, int T, int V, int M, int z0, int z1, int x0, int x1, sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * Box calibration (csrc/box_probe.hip; bench.py's "box" object -- no reference counterpart, measurement only): what the box
  * this process landed on sustains, so that a line's `frac` (against the guide's peaks) can be read next to `frac_of_box`.
  *   sar_box_mfma        dense loop of one matrix instruction: kind 0 = v_mfma_f32_32x32x2_f32, 1 = v_mfma_f32_32x32x16_f16,

@@ -64,6 +64,10 @@ def get_parser():
     parser.add_argument('--trainable-adjacency', action='store_true',
                         help="make the stacked adjacency a trainable variable `adjacency_matrix` (models/gcn.py AdjGraphConv); it is "
                              "trained only while epoch > --freeze-graph-until, as in the reference's train_step")
+    parser.add_argument('--pre-normalize', action='store_true',
+                        help="apply data_gen/preprocess.py `pre_normalization` (pad null frames, centre on the spine, hip->spine onto z, "
+                             "shoulders onto x) to every training and test batch on the device (csrc/prenorm.hip): for raw clips that "
+                             "did not go through data_gen/gen_joint_data.py; bone / motion streams are taken from the normalised joints")
     parser.add_argument('--verify-crc', default='full', choices=['full', 'length', 'off'],
                         help="TFRecord shards: 'full' checks the masked CRC-32C of every length field and payload (what tf.data's "
                              "reader does), 'length' the length fields only, 'off' the framing only")
@@ -99,7 +103,7 @@ def main():
     run_params = {k: v for k, v in vars(arg).items()
                   if k not in ("train_data_path", "test_data_path", "log_dir", "save_freq", "freeze_graph_until", "gpus", "resume",
                                "save_scores", "verify_crc") and not (k == "mfma" and v == "fp32")
-                  and not (k == "trainable_adjacency" and not v)}
+                  and not (k in ("trainable_adjacency", "pre_normalize") and not v)}
     run_name = str(run_params).replace(" ", "").replace("'", "").replace(",", "-")[1:-1]
     if arg.notes:
         run_name += "-" + arg.notes
@@ -112,6 +116,7 @@ def main():
         os.makedirs(ckpt_dir, exist_ok=True)
 
     from sar_amd.data import NpySkeletonData, SyntheticSkeletonData
+    from sar_amd import ops
     from sar_amd.train import Trainer, allreduce_sum_
     if arg.synthetic:
         train_data = SyntheticSkeletonData(arg.synthetic_size, arg.num_classes)
@@ -167,7 +172,7 @@ def main():
             next_iter = train_data.batches(arg.batch_size, rank, world, dev, shuffle=True, epoch=epoch)
         train_iter_obj, next_iter = next_iter, None
         for it, (x, y) in enumerate(train_iter_obj):
-            logits, loss = trainer.step(x, y)
+            logits, loss = trainer.step(ops.pre_normalize(x) if arg.pre_normalize else x, y)
             if trace_dir:
                 trace["ids"].append([epoch, x[:, 0, 0, 0, 0].tolist()])
             pending.append(torch.stack([loss.reshape(()) * 1.0, topk_correct(logits, y, 1).float() / global_batch_size,
@@ -197,7 +202,7 @@ def main():
             all_probs = []
             for it, (x, y) in enumerate(test_data.batches(arg.batch_size, 0, 1, dev, shuffle=False,
                                                           drop_remainder=False)):
-                probs = eng.predict(x)
+                probs = eng.predict(ops.pre_normalize(x) if arg.pre_normalize else x)
                 if checkpointing:      # main_gnn.py:410-416: confusion matrix of the test set (rows = true class)
                     cm.view(-1).index_add_(0, y * arg.num_classes + probs.argmax(1), torch.ones_like(y))
                     if arg.save_scores:

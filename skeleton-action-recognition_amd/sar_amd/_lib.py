@@ -203,6 +203,8 @@ SIGNATURES = {
     "sar_pool_bwd_cn8": (_i, [_fp, _i64, _i, _i, _i, _i, _fp, _fp]),
     "sar_cn_to_cn8": (_i, [_fp, _i64, _fp, _i64, _i, _i64, _fp]),
     "sar_cn8_to_cn": (_i, [_fp, _i64, _fp, _i64, _i, _i64, _fp]),
+    # pre-normalisation of raw clips (csrc/prenorm.hip)
+    "sar_pre_normalize_f32": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _fp]),
     # box calibration (bench.py "box"; csrc/box_probe.hip)
     "sar_box_mfma": (_i, [_i, _i, _i, _fp, _fp, _fp]),
     "sar_box_mfma_flops": (_i64, [_i, _i, _i]),

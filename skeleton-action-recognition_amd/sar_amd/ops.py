@@ -681,6 +681,24 @@ def transpose(inp, out, batch, R, Cc):
     check(L.load().sar_transpose_f32(ptr(inp), ptr(out), batch, R, Cc, stream_ptr()), "sar_transpose_f32")
 
 
+def pre_normalize(x, out=None, zaxis=(0, 1), xaxis=(8, 4)):
+    """data_gen/preprocess.py `pre_normalization` of a batch of raw clips (N, 3, T, V, M) on the device (csrc/prenorm.hip): null
+    frames padded by looping the clip, centred on body 0's joint 1, bone zaxis onto z, bone xaxis onto x.  Returns `out` (a new
+    tensor when None); `out` must not overlap x."""
+    _f32(x)
+    if x.dim() != 5 or x.shape[1] != 3:
+        raise L.SarError("pre_normalize: need (N, 3, T, V, M) coordinates, got %s" % (tuple(x.shape),))
+    if out is None:
+        out = torch.empty_like(x)
+    _f32(out)
+    if out.shape != x.shape:
+        raise L.SarError("pre_normalize: out %s does not match x %s" % (tuple(out.shape), tuple(x.shape)))
+    N, _, T, V, M = x.shape
+    check(L.load().sar_pre_normalize_f32(ptr(x), ptr(out), N, T, V, M, int(zaxis[0]), int(zaxis[1]), int(xaxis[0]), int(xaxis[1]),
+                                         stream_ptr()), "sar_pre_normalize_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ dense adjacency
 def graph_dense_fwd(y, A, out, K, F, V, nframes, stats=False, add=None):
     """out[m] = sum_k y[k F + m] . A_k (+ add[m]) (sar_graph_dense_fwd_f32); returns (partials, nparts) when stats."""
