@@ -11,7 +11,6 @@ y = block out) are materialised once in forward and kept for backward; BN+ReLU i
 consumer's operand load, BN statistics into the producer's epilogue.
 """
 import math
-
 import os
 
 import numpy as np
@@ -26,22 +25,24 @@ KS, KT = 3, 9        # kernel_size=[3, 9], models/stgcn.py:14
 # A block's weight gradients are ISSUED behind its data gradients in the fp32 engines (side stream as before): they then run
 # beside the NEXT block's element-wise BatchNorm passes instead of beside this block's data-gradient GEMMs.  Three interleaved
 # rounds: fp32 59.22 -> 58.99 ms per step; bf16 13.26 -> 13.55 (slower: there the order stays as it was).  SAR_WGRAD_DEFER=0/1 forces it.
-_WGRAD_DEFER_ENV = __import__("os").environ.get("SAR_WGRAD_DEFER")
-_FUSE_TAIL_F32 = __import__("os").environ.get("SAR_F32_FUSE_TAIL", "1") == "1"   # SAR_EPI_ADD_GATE in the fp32 graph data gradient
+_WGRAD_DEFER_ENV = os.environ.get("SAR_WGRAD_DEFER")
+# SAR_EPI_ADD_GATE in the fp32 graph data gradient
+_FUSE_TAIL_F32 = os.environ.get("SAR_F32_FUSE_TAIL", "1") == "1"
 # the arithmetic an STGCN built without an explicit `mfma` uses (the parity suites run once per value: tests/conftest.py)
-DEFAULT_MFMA = __import__("os").environ.get("SAR_MFMA", "fp32")
-SPLIT_ARITH = {"f32_split": "f16x3a", "f32_split_bf16x6": "bf16x6"}      # engine mode -> arithmetic of csrc/conv_gemm_split.hip
-# A/B switch: which kernel families of a split engine take the split kernels (default all that are built)
-# the skip gradient of a conv-residual block as its even frames only: "fp32" (default) = the fp32-arithmetic engine, where it measured
-# +0.4 % (58.70 -> 58.47 ms, interleaved); "1" = the split engines too (single stream -0.29 ms, two streams 34.34 -> 34.44 ms: not taken);
-# "0" = never (gpurun_out/compact_skip_ab*.txt, DESIGN 3.11e)
+DEFAULT_MFMA = os.environ.get("SAR_MFMA", "fp32")
+# engine mode -> arithmetic of csrc/conv_gemm_split.hip
+SPLIT_ARITH = {"f32_split": "f16x3a", "f32_split_bf16x6": "bf16x6"}
 # SAR_STGCN_AUX_STREAM=0: the split engine's term images, the zeroing of its bound cells and its Samuelson cells on the main stream again
 # instead of on a third stream beside the data_bn stage and the first layer (round 6, as sar_amd/resnet.py; bit-identical).  One bench.py
 # process per entry (profiles/r06_stgcn_aux_stream_ab.txt): f32_split 1 929 -> 1 936 clips/s (+0.3 %); the bf16 engine's single pack launch
 # forked the same way: 5 497 -> 5 466 (-0.5 %), not forked
-AUX_STREAM = __import__("os").environ.get("SAR_STGCN_AUX_STREAM", "1") == "1"
-_COMPACT_SKIP = __import__("os").environ.get("SAR_COMPACT_SKIP", "fp32")
-_SPLIT_KINDS = set(__import__("os").environ.get("SAR_SPLIT_KINDS", "tfwd,tdgrad,twgrad,gfwd,gdgrad,gwgrad,rfwd,rdgrad,rwgrad").split(","))
+AUX_STREAM = os.environ.get("SAR_STGCN_AUX_STREAM", "1") == "1"
+# the skip gradient of a conv-residual block as its even frames only: "fp32" (default) = the fp32-arithmetic engine, where it measured
+# +0.4 % (58.70 -> 58.47 ms, interleaved); "1" = the split engines too (single stream -0.29 ms, two streams 34.34 -> 34.44 ms: not taken);
+# "0" = never (gpurun_out/compact_skip_ab*.txt, DESIGN 3.11e)
+_COMPACT_SKIP = os.environ.get("SAR_COMPACT_SKIP", "fp32")
+# A/B switch: which kernel families of a split engine take the split kernels (default all that are built)
+_SPLIT_KINDS = set(os.environ.get("SAR_SPLIT_KINDS", "tfwd,tdgrad,twgrad,gfwd,gdgrad,gwgrad,rfwd,rdgrad,rwgrad").split(","))
 # (filters, stride, residual) -- models/stgcn.py:113-123
 BLOCKS = [(64, 1, False), (64, 1, True), (64, 1, True), (64, 1, True), (128, 2, True), (128, 1, True), (128, 1, True),
           (256, 2, True), (256, 1, True), (256, 1, True)]
@@ -71,10 +72,12 @@ class _BN:
 
 
 class STGCN:
-    # split arithmetic (mfma="f32_split*"): off unless __init__ turns it on (subclasses with their own __init__ -- ST-GIN -- are fp32)
-    mfma, split, spacked, _cells = "fp32", None, None, None
-    _slabs, _slab_flush = None, "end"     # (ops.SlabBatch of the weight gradients: set by __init__; ST-GIN keeps its per-gradient reductions)
-    _aux, _aux_pending, _bounds_forked = None, False, False     # (third stream: set by __init__; engines with their own __init__ have none)
+    # What a sibling engine (sar_amd/stgin.py, stpgcn.py, stgcn_ta.py) declares about itself; __init__ and the gates below read these:
+    env_arithmetic = True      # built without `mfma`: DEFAULT_MFMA (the siblings are fp32)
+    batched_slabs = True       # one slab reduction per gradient bucket (ops.SlabBatch) instead of one per weight gradient
+    third_stream = True        # the aux stream of forward() (AUX_STREAM)
+    batched_wT = True          # one re-layout launch for every data-gradient operand (_wT) instead of one transpose per layer
+    stock_backward = True      # blocks run STGCN._block_backward: the fused fp32 tail and the compact skip gradient apply
 
     def __init__(self, num_classes=60, in_channels=3, num_node=25, A=None, device="cuda", seed=0, bone_pairs=None,
                  blocks=None, motion=False, mfma=None, trainable_adjacency=False):
@@ -90,7 +93,7 @@ class STGCN:
         # accumulation: csrc/conv_gemm_split.hip; same parity tolerances as "fp32").  "f32_split_bf16x6": three bfloat16 terms,
         # six products (no operand scaling).  Kernels without a split form, and inference, stay on the fp32 kernels.
         if mfma is None:
-            mfma = DEFAULT_MFMA if (type(self) is STGCN and not trainable_adjacency) else "fp32"
+            mfma = DEFAULT_MFMA if (self.env_arithmetic and not trainable_adjacency) else "fp32"
         assert mfma in ("fp32", "bf16", "bf16_operands", "f32_split", "f32_split_bf16x6")
         self.mfma = mfma
         self.cn8 = mfma == "bf16"
@@ -104,56 +107,81 @@ class STGCN:
         self.dense_A = bool(trainable_adjacency)
         self.train_adjacency = True
         assert not (self.dense_A and mfma != "fp32"), "trainable adjacency is built for the fp32 engine"
-        self.device = torch.device(device)
         self.num_classes, self.C_in, self.V = num_classes, in_channels, num_node
         self.blocks = list(blocks if blocks is not None else BLOCKS)
+        # every engine of the family runs these steps, in this order; a sibling overrides the step that differs
+        self._init_device(device, bone_pairs, motion)
+        self._init_adjacency(A)
+        self._declare_params()
+        total = self._allocate()
+        self._init_bn()
+        self._init_operand_images()
+        self._init_params(seed)
+        self._saved = None
+        self._deferred, self._flushing = [], False
+        self._buckets = self._make_buckets(total)
+
+    # ------------------------------------------------------------------ the constructor's steps
+    def _init_device(self, device, bone_pairs, motion):
+        self.device = dev = torch.device(device)
+        # the weight-gradient stream; SAR_WGRAD_PRIO: its priority (torch convention: lower = more urgent; default 0 = same as
+        # the main chain)
+        self._side = (ops.shared_side_stream(dev, int(os.environ.get("SAR_WGRAD_PRIO", "0")))
+                      if dev.type == "cuda" and os.environ.get("SAR_WGRAD_STREAM", "1") == "1" else None)
+        self._slabs = ops.SlabBatch() if (ops.SLAB_BATCH and self.batched_slabs) else None
+        self._slab_flush = ops.SLAB_FLUSH
+        self._aux = ops.shared_aux_stream(dev) if (AUX_STREAM and self.third_stream and dev.type == "cuda") else None
+        self._aux_pending = self._bounds_forked = False
+        self.motion = bool(motion)   # motion stream (data_gen/gen_motion_data.py:24-27) of the joint / bone data, on the fly
+        self.bone_parent = None
+        if bone_pairs is not None:
+            bp = np.full(self.V, -1, dtype=np.int32)
+            for v1, v2 in bone_pairs:          # data_gen/gen_bone_data.py:36-41 (1-based pairs)
+                bp[v1 - 1] = v2 - 1
+            self.bone_parent = torch.from_numpy(bp).to(dev)
+
+    def _init_adjacency(self, A):
         A = np.asarray(ntu_adjacency() if A is None else A, dtype=np.float64)
-        assert A.shape == (KS, num_node, num_node)
+        assert A.shape == (KS, self.V, self.V)
         self.A_host = A.astype(np.float32)
         self.A = torch.from_numpy(self.A_host).to(self.device)     # 'adjacency_matrix', non-trainable (stgcn.py:105-109)
         self.tab_fwd = ops.GraphTables(self.A_host, self.device, transpose=False)
         self.tab_bwd = ops.GraphTables(self.A_host, self.device, transpose=True)
-        # the weight-gradient stream; SAR_WGRAD_PRIO: its priority (torch convention: lower = more urgent; default 0 = same as
-        # the main chain)
-        self._side = (ops.shared_side_stream(self.device, int(os.environ.get("SAR_WGRAD_PRIO", "0")))
-                      if self.device.type == "cuda" and os.environ.get("SAR_WGRAD_STREAM", "1") == "1" else None)
-        self._slabs = ops.SlabBatch() if ops.SLAB_BATCH else None     # one slab reduction per gradient bucket (ops.SlabBatch)
-        self._slab_flush = ops.SLAB_FLUSH
-        self._aux = ops.shared_aux_stream(self.device) if (AUX_STREAM and self.device.type == "cuda" and type(self) is STGCN) else None
-        self.motion = bool(motion)   # motion stream (data_gen/gen_motion_data.py:24-27) of the joint / bone data, on the fly
-        self.bone_parent = None
-        if bone_pairs is not None:
-            bp = np.full(num_node, -1, dtype=np.int32)
-            for v1, v2 in bone_pairs:          # data_gen/gen_bone_data.py:36-41 (1-based pairs)
-                bp[v1 - 1] = v2 - 1
-            self.bone_parent = torch.from_numpy(bp).to(self.device)
 
-        # ---- parameter table (Keras layouts), flat storage
-        self.shapes = {}
-        nch = num_node * in_channels
+    def _declare_params(self):
+        """the parameter table (Keras layouts and names), in the order of the flat buffer"""
+        self.shapes, self.kinds = {}, []
+        nch = self.V * self.C_in
         self._add("data_bn.gamma", (nch,)), self._add("data_bn.beta", (nch,))
-        cin = in_channels
-        self.kinds = []
+        cin = self.C_in
         for i, (f, s, res) in enumerate(self.blocks):
-            pre = "l%d." % i
             kind = "none" if not res else ("identity" if (cin == f and s == 1) else "conv")   # stgcn.py:41-56
             self.kinds.append(kind)
-            self._add(pre + "gcn.kernel", (1, 1, cin, KS * f)), self._add(pre + "gcn.bias", (KS * f,))
-            self._add(pre + "bn1.gamma", (f,)), self._add(pre + "bn1.beta", (f,))
-            self._add(pre + "tcn.kernel", (KT, 1, f, f)), self._add(pre + "tcn.bias", (f,))
-            self._add(pre + "bn2.gamma", (f,)), self._add(pre + "bn2.beta", (f,))
-            if kind == "conv":
-                self._add(pre + "res.kernel", (1, 1, cin, f)), self._add(pre + "res.bias", (f,))
-                self._add(pre + "res_bn.gamma", (f,)), self._add(pre + "res_bn.beta", (f,))
+            self._declare_block("l%d." % i, cin, f, kind)
             self._params_after_block(i)
             cin = f
         self.C_last = cin
-        self._add("logits.kernel", (1, 1, cin, num_classes)), self._add("logits.bias", (num_classes,))
+        self._add("logits.kernel", (1, 1, cin, self.num_classes)), self._add("logits.bias", (self.num_classes,))
         if self.dense_A and self._shared_adjacency():
-            self._add("adjacency_matrix", (KS, num_node, num_node))
-        # flat storage: every offset is a multiple of 4 floats so that each weight view is 16-byte aligned
-        # (the GEMM kernels stage weight rows as float4); a bias stays glued to its kernel because the
-        # weight-gradient slabs are reduced as one contiguous [kernel | bias] range.
+            self._add("adjacency_matrix", (KS, self.V, self.V))
+
+    def _declare_block(self, pre, cin, f, kind):
+        self._add(pre + "gcn.kernel", (1, 1, cin, KS * f)), self._add(pre + "gcn.bias", (KS * f,))
+        self._declare_temporal(pre, f, cin, f, kind)
+
+    def _declare_temporal(self, pre, c, cin, f, kind):
+        """what follows a block's spatial operator (c channels): bn1, the temporal convolution c -> f, bn2, the residual branch"""
+        self._add(pre + "bn1.gamma", (c,)), self._add(pre + "bn1.beta", (c,))
+        self._add(pre + "tcn.kernel", (KT, 1, c, f)), self._add(pre + "tcn.bias", (f,))
+        self._add(pre + "bn2.gamma", (f,)), self._add(pre + "bn2.beta", (f,))
+        if kind == "conv":
+            self._add(pre + "res.kernel", (1, 1, cin, f)), self._add(pre + "res.bias", (f,))
+            self._add(pre + "res_bn.gamma", (f,)), self._add(pre + "res_bn.beta", (f,))
+
+    def _allocate(self):
+        """flat storage: every offset is a multiple of 4 floats so that each weight view is 16-byte aligned (the GEMM kernels stage
+        weight rows as float4); a bias stays glued to its kernel because the weight-gradient slabs are reduced as one contiguous
+        [kernel | bias] range.  Returns the buffer's length."""
         total, self.offsets = 0, {}
         for k, shp in self.shapes.items():
             n = int(np.prod(shp))
@@ -162,111 +190,90 @@ class STGCN:
             self.offsets[k] = total
             total += n if k.endswith(".kernel") else (n + 3) // 4 * 4
         self.n_params = sum(int(np.prod(shp)) for shp in self.shapes.values())
-        dev = self.device
-        self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.velocity = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.flat, self.grad, self.velocity, self.lr_dev = z(total), z(total), z(total), z(1)
         self._lr_host = None      # the value lr_dev holds (sgd_step skips the fill while the schedule keeps the rate); None = unknown
-        self.packed = None
-        if self.cn8:       # bf16 operand images of EVERY conv weight, both orientations, refreshed by one launch per forward
-            pk = ops.PackedWeights()
-            cin = in_channels
-            for i, (f, s_, res) in enumerate(self.blocks):
-                pre = "l%d." % i
-                og, ot = self.offsets[pre + "gcn.kernel"], self.offsets[pre + "tcn.kernel"]
-                pk.add(pre + "gcn.f", og, f, KS * f, 1, KS, cin, f)          # (k, c, m) = kernel[c][k*F + m]
-                pk.add(pre + "gcn.b", og, f, 1, KS * f, KS, f, cin)          # (k, c', m') = kernel[m'][k*F + c']
-                pk.add(pre + "tcn.f", ot, f * f, f, 1, KT, f, f)             # (tap, c, m) = kernel[tap][c][m]
-                pk.add(pre + "tcn.b", ot, f * f, 1, f, KT, f, f)             # (tap, c', m') = kernel[tap][m'][c']
-                if self.kinds[i] == "conv":
-                    orr = self.offsets[pre + "res.kernel"]
-                    pk.add(pre + "res.f", orr, 0, f, 1, 1, cin, f)
-                    pk.add(pre + "res.b", orr, 0, 1, f, 1, f, cin)
-                cin = f
-            pk.finalize(dev)
-            self.packed = pk
-        if self.bf16:      # bf16 operand images of every conv weight, both orientations, refreshed by one launch per forward
-            pk = ops.PackedWeights()
-            cin = in_channels
-            for i, (f, s_, res) in enumerate(self.blocks):
-                pre = "l%d." % i
-                og, ot = self.offsets[pre + "gcn.kernel"], self.offsets[pre + "tcn.kernel"]
-                if f % 8 == 0 and cin >= 16:
-                    pk.add(pre + "gcn.f", og, f, KS * f, 1, KS, cin, f)          # (k, c, m) = kernel[c][k*F + m]
-                if cin % 8 == 0 and f >= 16:
-                    pk.add(pre + "gcn.b", og, f, 1, KS * f, KS, f, cin)          # (k, c', m') = kernel[m'][k*F + c']
-                if f % 8 == 0 and f >= 16:
-                    pk.add(pre + "tcn.f", ot, f * f, f, 1, KT, f, f)             # (tap, c, m) = kernel[tap][c][m]
-                    pk.add(pre + "tcn.b", ot, f * f, 1, f, KT, f, f)             # (tap, c', m') = kernel[tap][m'][c']
-                if self.kinds[i] == "conv":
-                    orr = self.offsets[pre + "res.kernel"]
-                    if f % 8 == 0 and cin >= 16:
-                        pk.add(pre + "res.f", orr, 0, f, 1, 1, cin, f)
-                    if cin % 8 == 0 and f >= 16:
-                        pk.add(pre + "res.b", orr, 0, 1, f, 1, f, cin)
-                cin = f
-            if pk.items:
-                pk.finalize(dev)
-                self.packed = pk
-        self.spacked, self._cells = None, None
-        if self.split:     # term images of the conv weights the split kernels take, both orientations, one refresh per step
-            pk = ops.PackedSplitWeights(self.split)
-            cin = in_channels
-            for i, (f, s_, res) in enumerate(self.blocks):
-                pre = "l%d." % i
-                og, ot = self.offsets[pre + "gcn.kernel"], self.offsets[pre + "tcn.kernel"]
-                if ops.split_applicable(L.SAR_CONV_GRAPH, num_node, cin, f, KS, 1, self.tab_fwd):
-                    pk.add(pre + "gcn.f", og, f, KS * f, 1, KS, cin, f)          # (k, c, m) = kernel[c][k*F + m]
-                if ops.split_applicable(L.SAR_CONV_GRAPH, num_node, f, cin, KS, 1, self.tab_bwd):
-                    pk.add(pre + "gcn.b", og, f, 1, KS * f, KS, f, cin)          # (k, c', m') = kernel[m'][k*F + c']
-                if self.kinds[i] == "conv" and self.split in ("f16x3a", "bf16x6"):
-                    # the strided 1x1 residual convolution and the dense 1x1 product of its data gradient (conv_tap1_split_kernel, round 6)
-                    orr = self.offsets[pre + "res.kernel"]
-                    if ops.split_applicable(L.SAR_CONV_TEMPORAL, num_node, cin, f, 1, s_):
-                        pk.add(pre + "res.f", orr, 0, f, 1, 1, cin, f)           # (0, c, m) = kernel[c][m]
-                    if s_ == 2 and ops.split_applicable(L.SAR_CONV_TEMPORAL, num_node, f, cin, 1, 1):
-                        pk.add(pre + "res.b", orr, 0, 1, f, 1, f, cin)           # (0, c', m') = kernel[m'][c']
-                cin = f
-                if ops.split_applicable(L.SAR_CONV_TEMPORAL, num_node, f, f, KT, s_):
-                    pk.add(pre + "tcn.f", ot, f * f, f, 1, KT, f, f)             # (tap, c, m) = kernel[tap][c][m]
-                    pk.add(pre + "tcn.b", ot, f * f, 1, f, KT, f, f)             # (tap, c', m') = kernel[tap][m'][c']
-            if pk.items:
-                pk.finalize(dev)
-                self.spacked = pk
-            # operand bounds of the fp16 arithmetic (include/sar_hip.h: cells), zeroed at the start of every training step
-            self._cells = torch.zeros(8 * len(self.blocks), dtype=torch.int32, device=dev)
-        # fp32 operands of the data-gradient GEMMs ((tap, f, c) / (k*F + f, c) / (f, c) transposes of the kernels): ONE
-        # re-layout launch at the start of backward() instead of one small dependent launch in front of every data gradient
-        # (22 per step, each on the critical chain)
-        self._wT_off, self._wT_perm, self._wT = {}, None, None
-        if not self.cn8:
-            pb, off, cin = ops.PermuteBatch(), 0, in_channels
-            for i, (f, s_, res) in enumerate(self.blocks):
-                pre = "l%d." % i
-                pb.add(self.offsets[pre + "tcn.kernel"], off, KT, f, f, f * f, 1, f)        # [tap][c][f] -> [tap][f][c]
-                self._wT_off[pre + "tcn"], off = off, off + KT * f * f
-                pb.add(self.offsets[pre + "gcn.kernel"], off, 1, KS * f, cin, 0, 1, KS * f)  # [c][k*F+f] -> [k*F+f][c]
-                self._wT_off[pre + "gcn"], off = off, off + KS * f * cin
-                if self.kinds[i] == "conv":
-                    pb.add(self.offsets[pre + "res.kernel"], off, 1, f, cin, 0, 1, f)       # [c][f] -> [f][c]
-                    self._wT_off[pre + "res"], off = off, off + f * cin
-                cin = f
-            pb.finalize(dev)
-            self._wT_perm, self._wT = pb, torch.zeros(off, dtype=torch.float32, device=dev)
         self.p = {k: self._view(self.flat, k) for k in self.shapes}
         self.g = {k: self._view(self.grad, k) for k in self.shapes}
         if "adjacency_matrix" in self.p:
             self.A = self.p["adjacency_matrix"]          # the trainable copy (initialised from the graph in _init_params)
-        self.bn = {"data_bn": _BN(nch, dev)}
+        return total
+
+    def _init_bn(self):
+        self.bn = {"data_bn": _BN(self.V * self.C_in, self.device)}
         for i, (f, s, res) in enumerate(self.blocks):
-            self.bn["l%d.bn1" % i], self.bn["l%d.bn2" % i] = _BN(f, dev), _BN(f, dev)
+            self._init_block_bn("l%d." % i, f, self.kinds[i])
+
+    def _init_block_bn(self, pre, f, kind, c=None):
+        """c: channels of the spatial operator's output where they are not f"""
+        self.bn[pre + "bn1"], self.bn[pre + "bn2"] = _BN(c or f, self.device), _BN(f, self.device)
+        if kind == "conv":
+            self.bn[pre + "res_bn"] = _BN(f, self.device)
+
+    def _weight_images(self):
+        """Every convolution weight as a GEMM operand in both orientations -- .f the forward launch, .b the data gradient (the same
+        tensor with the roles of c and m exchanged) -- block by block: (key, block index, (src_off, st, sc, sm, taps, Kc, M)) with
+        element (tap, c, m) at flat[src_off + tap * st + c * sc + m * sm]"""
+        cin = self.C_in
+        for i, (f, s, res) in enumerate(self.blocks):
+            pre = "l%d." % i
+            ot, og = self.offsets[pre + "tcn.kernel"], self.offsets[pre + "gcn.kernel"]
+            yield pre + "tcn.f", i, (ot, f * f, f, 1, KT, f, f)              # (tap, c, m) = kernel[tap][c][m]
+            yield pre + "tcn.b", i, (ot, f * f, 1, f, KT, f, f)              # (tap, c', m') = kernel[tap][m'][c']
+            yield pre + "gcn.f", i, (og, f, KS * f, 1, KS, cin, f)           # (k, c, m) = kernel[c][k*F + m]
+            yield pre + "gcn.b", i, (og, f, 1, KS * f, KS, f, cin)           # (k, c', m') = kernel[m'][k*F + c']
             if self.kinds[i] == "conv":
-                self.bn["l%d.res_bn" % i] = _BN(f, dev)
-        self._init_params(seed)
-        self._saved = None
-        self._deferred, self._flushing = [], False
-        self._buckets = self._make_buckets(total)
+                orr = self.offsets[pre + "res.kernel"]
+                yield pre + "res.f", i, (orr, 0, f, 1, 1, cin, f)            # (0, c, m) = kernel[c][m]
+                yield pre + "res.b", i, (orr, 0, 1, f, 1, f, cin)            # (0, c', m') = kernel[m'][c']
+            cin = f
+
+    def _pack(self, pk, admit):
+        """the images of _weight_images() that admit(key, stride of the block, taps, Kc, M) takes, refreshed by one launch per step"""
+        for key, i, w in self._weight_images():
+            if admit(key, self.blocks[i][1], *w[4:]):
+                pk.add(key, *w)
+        if not pk.items:
+            return None
+        pk.finalize(self.device)
+        return pk
+
+    def _split_admits(self, key, s, taps, Kc, M):
+        """the shapes csrc/conv_gemm_split.hip is built for; the 1x1 residual convolution (conv_tap1_split_kernel, round 6): its strided
+        forward form and the dense product of the compact skip gradient of a stride-2 block"""
+        layer, way = key.split(".")[1:]
+        if layer == "gcn":
+            return ops.split_applicable(L.SAR_CONV_GRAPH, self.V, Kc, M, taps, 1, self.tab_fwd if way == "f" else self.tab_bwd)
+        if layer == "tcn":
+            return ops.split_applicable(L.SAR_CONV_TEMPORAL, self.V, Kc, M, taps, s)
+        return (self.split in ("f16x3a", "bf16x6") and (way == "f" or s == 2)
+                and ops.split_applicable(L.SAR_CONV_TEMPORAL, self.V, Kc, M, 1, s if way == "f" else 1))
+
+    def _init_operand_images(self):
+        """what the arithmetic needs beside the fp32 parameters: bf16 operand images (cn8: of EVERY conv weight), the split engines'
+        term images and operand-bound cells, the fp32 engines' transposed data-gradient operands"""
+        dev = self.device
+        self.packed = self.spacked = self._cells = None
+        if self.cn8:
+            self.packed = self._pack(ops.PackedWeights(), lambda key, s, taps, Kc, M: True)
+        if self.bf16:
+            self.packed = self._pack(ops.PackedWeights(), lambda key, s, taps, Kc, M: M % 8 == 0 and Kc >= 16)
+        if self.split:
+            self.spacked = self._pack(ops.PackedSplitWeights(self.split), self._split_admits)
+            # operand bounds of the fp16 arithmetic (include/sar_hip.h: cells), zeroed at the start of every training step
+            self._cells = torch.zeros(8 * len(self.blocks), dtype=torch.int32, device=dev)
+        # fp32 operands of the data-gradient GEMMs ((tap, f, c) / (k, f, c) / (f, c) transposes of the kernels): ONE
+        # re-layout launch at the start of backward() instead of one small dependent launch in front of every data gradient
+        # (22 per step, each on the critical chain)
+        self._wT_off, self._wT_perm, self._wT = {}, None, None
+        if self.batched_wT and not self.cn8:
+            pb, off = ops.PermuteBatch(), 0
+            for key, i, (src, st, sc, sm, taps, Kc, M) in self._weight_images():
+                if key.endswith(".b"):
+                    pb.add(src, off, taps, Kc, M, st, sc, sm)          # [tap][Kc][M], contiguous
+                    self._wT_off[key[:-2]], off = off, off + taps * Kc * M
+            pb.finalize(dev)
+            self._wT_perm, self._wT = pb, torch.zeros(off, dtype=torch.float32, device=dev)
 
     # ------------------------------------------------------------------ gradient buckets (data-parallel exchange)
     def _make_buckets(self, total):
@@ -309,21 +316,20 @@ class STGCN:
     def _flush_slabs(self):
         """the slabs of every weight gradient issued since the last flush are summed by ONE launch on the weight-gradient stream
         (ops.SlabBatch): before a bucket is handed to the all-reduce and at the end of backward()"""
-        slabs = getattr(self, "_slabs", None)
-        if slabs is None:
+        if self._slabs is None:
             return
         if self._side is None:
-            slabs.flush()
+            self._slabs.flush()
         else:
             with torch.cuda.stream(self._side):
-                slabs.flush()
+                self._slabs.flush()
 
     def _buckets_after_block(self, i, cb):
         if cb is not None:
             for bi, (blk, _, _) in enumerate(self._buckets):
                 if blk == i:
                     self._bucket_done(bi, cb)
-        elif getattr(self, "_slabs", None) is not None and (
+        elif self._slabs is not None and (
                 self._slab_flush == "block" or (self._slab_flush == "bucket" and any(blk == i for blk, _, _ in self._buckets))):
             self._flush_slabs()      # (experiment switch SAR_SLAB_FLUSH: more, smaller slab reductions than one at the end of backward)
 
@@ -429,11 +435,17 @@ class STGCN:
         return {k: v for k, v in self.g.items()}
 
     # ------------------------------------------------------------------ forward
-    def _bn_forward_stats(self, name, partials, nparts, count, training, unbiased):
+    def _bn_forward(self, name, result, count, training, unbiased=True):
+        """BatchNorm `name` ready for its consumer's operand load (scale, shift): training, from the statistics its producer's epilogue
+        left in result = (partials, nparts, ..) over `count` samples, the moving statistics updated; inference, from the moving
+        statistics.  Returns the _BN."""
         b = self.bn[name]
-        ops.bn_finalize(partials, nparts, b.mean.numel(), count, BN_EPS, BN_MOMENTUM, unbiased, self.p[name + ".gamma"],
-                        self.p[name + ".beta"], b.moving_mean if training else None, b.moving_var if training else None,
-                        b.mean, b.rstd, b.scale, b.shift)
+        if training:
+            ops.bn_finalize(result[0], result[1], b.mean.numel(), count, BN_EPS, BN_MOMENTUM, unbiased, self.p[name + ".gamma"],
+                            self.p[name + ".beta"], b.moving_mean, b.moving_var, b.mean, b.rstd, b.scale, b.shift)
+        else:
+            self._bn_eval(name)
+        return b
 
     def _bn_eval(self, name):
         b = self.bn[name]
@@ -473,14 +485,11 @@ class STGCN:
                 self.spacked.refresh(self.flat)
                 self._cells.zero_()
         # ---- data_bn (models/stgcn.py:142-147)
-        nch = V * Cin
+        part = None
         if training:
-            part = torch.empty((nch, N, 2), dtype=torch.float32, device=dev)
+            part = torch.empty((V * Cin, N, 2), dtype=torch.float32, device=dev)
             ops.data_bn_stats(x, self.bone_parent, part, self.motion)
-            self._bn_forward_stats("data_bn", part, N, N * M * T, True, False)
-        else:
-            self._bn_eval("data_bn")
-        dbn = self.bn["data_bn"]
+        dbn = self._bn_forward("data_bn", (part, N), N * M * T, training, unbiased=False)
         h = torch.empty((Cin, B * T * V), dtype=torch.float32, device=dev)
         ops.data_bn_apply(x, self.bone_parent, dbn.scale, dbn.shift, h, self.motion)
         if keep is not None:
@@ -525,11 +534,7 @@ class STGCN:
             r1 = ops.conv_gemm(L.SAR_CONV_GRAPH, X, g, self.p[pre + "gcn.kernel"], f, KS * f, B=B, V=V, T_src=T, T_out=T,
                                Kc=cin, M=f, taps=KS, bias=self.p[pre + "gcn.bias"], tables=self.tab_fwd, epi=epi,
                                **self._split_args(gimg, self._cell(i, 3), self._img(pre + "gcn.f")))
-        if training:
-            self._bn_forward_stats(pre + "bn1", r1[0], r1[1], n_in, True, True)
-        else:
-            self._bn_eval(pre + "bn1")
-        bn1 = self.bn[pre + "bn1"]
+        bn1 = self._bn_forward(pre + "bn1", r1, n_in, training)
         # tgcn: BN -> ReLU folded into the operand load, Conv2D [9,1] stride s SAME (models/stgcn.py:26-36)
         u = torch.empty((f, n_out), dtype=torch.float32, device=dev)
         simg = self._simg(pre + "tcn.f") if training else None        # inference keeps the fp32 kernels (no batch statistics to bound with)
@@ -540,11 +545,7 @@ class STGCN:
                            Kc=f, M=f, taps=KT, stride=s, pad=pad, bias=self.p[pre + "tcn.bias"],
                            pro=(bn1.scale, bn1.shift), pro_relu=True, epi=epi,
                            **self._split_args(simg, self._cell(i, 0), self._img(pre + "tcn.f")))
-        if training:
-            self._bn_forward_stats(pre + "bn2", r2[0], r2[1], n_out, True, True)
-        else:
-            self._bn_eval(pre + "bn2")
-        bn2 = self.bn[pre + "bn2"]
+        bn2 = self._bn_forward(pre + "bn2", r2, n_out, training)
         r = None
         rbn = None
         if kind == "conv":  # models/stgcn.py:47-56
@@ -553,11 +554,7 @@ class STGCN:
             r3 = ops.conv_gemm(L.SAR_CONV_TEMPORAL, X, r, self.p[pre + "res.kernel"], 0, f, B=B, V=V, T_src=T, T_out=To,
                                Kc=cin, M=f, taps=1, stride=s, pad=0, bias=self.p[pre + "res.bias"], epi=epi,
                                **self._split_args(rsimg, self._cell(i, 3), self._img(pre + "res.f")))
-            if training:
-                self._bn_forward_stats(pre + "res_bn", r3[0], r3[1], n_out, True, True)
-            else:
-                self._bn_eval(pre + "res_bn")
-            rbn = self.bn[pre + "res_bn"]
+            rbn = self._bn_forward(pre + "res_bn", r3, n_out, training)
         y = torch.empty((f, n_out), dtype=torch.float32, device=dev)
         res_kind = {"none": 0, "identity": 1, "conv": 2}[kind]
         ymask = ops.relu_mask(y) if training else None     # 1 bit per element: what the BatchNorm-backward passes read instead of y
@@ -682,15 +679,11 @@ class STGCN:
         gated = None
         for i in reversed(range(len(self.blocks))):
             dY = self._after_block_backward(i, dY, B)
-            if fuse:
-                sbb = sv["blocks"][i - 1] if i >= 1 else None
-                # (a layer between the blocks adds its own gradient first: no gating of block i - 1 inside block i's data gradient)
-                below = sbb if (sbb is not None and self.kinds[i - 1] != "conv" and sbb.get("ymask") is not None
-                                and sv["blocks"][i]["kind"] != "none" and sv["blocks"][i]["cin"] % 8 == 0
-                                and not self._layer_after(i - 1)) else None
-                dY, gated = self._block_backward(i, sv["blocks"][i], dY, B, gated, below)
-            else:
-                dY = self._block_backward(i, sv["blocks"][i], dY, B)
+            sb, sbb = sv["blocks"][i], sv["blocks"][i - 1] if i >= 1 else None
+            # (a layer between the blocks adds its own gradient first: no gating of block i - 1 inside block i's data gradient)
+            below = sbb if (fuse and sbb is not None and self.kinds[i - 1] != "conv" and sbb.get("ymask") is not None
+                            and sb["kind"] != "none" and sb["cin"] % 8 == 0 and not self._layer_after(i - 1)) else None
+            dY, gated = self._block_backward(i, sb, dY, B, gated, below)
             if self._deferred:
                 self._flush_deferred()
             self._buckets_after_block(i, bucket_cb)
@@ -700,23 +693,48 @@ class STGCN:
         x = sv["x"]
         nch = V * self.C_in
         part = torch.empty((nch, N, 2), dtype=torch.float32, device=dev)
-        dbn = self.bn["data_bn"]
-        ops.data_bn_bwd_reduce(x, self.bone_parent, dY, dbn.mean, part, self.motion)
-        ops.bn_bwd_finalize(part, N, N * 2, 2, 0, 1, nch, N * M * sv["T"], self.p["data_bn.gamma"], dbn.mean, dbn.rstd,
-                            self.g["data_bn.gamma"], self.g["data_bn.beta"])
+        ops.data_bn_bwd_reduce(x, self.bone_parent, dY, self.bn["data_bn"].mean, part, self.motion)
+        self._bn_backward("data_bn", (part, N), 2, 1, N * M * sv["T"], coefficients=False)
         self._finish_backward(bucket_cb)
 
     def _fuse_tail_f32(self):
         """SAR_EPI_ADD_GATE in the fp32 graph data gradient (SAR_F32_FUSE_TAIL=0 turns it off): plain ST-GCN engine, fp32 MFMA
         operands, gather tables, ReLU masks written by the forward tails"""
-        return (_FUSE_TAIL_F32 and type(self)._block_backward is STGCN._block_backward and not self.bf16 and not self.dense_A
-                and not getattr(self, "cn8", False) and ops.RELU_MASK and not ops.BN_TAIL)
+        return (_FUSE_TAIL_F32 and self.stock_backward and not self.bf16 and not self.dense_A and not self.cn8
+                and ops.RELU_MASK and not ops.BN_TAIL)
+
+    def _bn_backward(self, name, sums, per, which, count, coefficients=True):
+        """gamma / beta gradients of BatchNorm `name` and the coefficients k1..k3 of its backward apply pass, from sums = (partials,
+        nparts, ..) of `per` sums per channel and partial over `count` samples; `which`: the second sum's position"""
+        b = self.bn[name]
+        ops.bn_bwd_finalize(sums[0], sums[1], sums[1] * per, per, 0, which, b.mean.numel(), count, self.p[name + ".gamma"], b.mean,
+                            b.rstd, self.g[name + ".gamma"], self.g[name + ".beta"], *((b.k1, b.k2, b.k3) if coefficients else ()))
+
+    def _tail_backward_sums(self, pre, sb, dY, n_out, gated, reduce):
+        """Backward of the block tail y = relu(bn2(u) + res) (models/stgcn.py:37,62-63) up to its apply pass: the BatchNorm-backward
+        sums of bn2 (and res_bn) finalised.  gated: the sums came with dY; else `reduce` (the engine's bn_add_relu_bwd_reduce)
+        produces them, with ops.BN_TAIL its last workgroup per channel finalises as well (no launch between)."""
+        y, u, kind = sb["y"], sb["u"], sb["kind"]
+        bn2, rbn = self.bn[pre + "bn2"], self.bn.get(pre + "res_bn")
+        r, rmean = (sb["r"], rbn.mean) if kind == "conv" else (None, None)
+        if gated is not None:    # (sum dz, sum dz (u - mean)) per channel and partial
+            assert kind != "conv"
+            self._bn_backward(pre + "bn2", gated, 2, 1, n_out)
+        elif ops.BN_TAIL:
+            tail = ops.make_bn_tail(dY.device, n_out, self.p[pre + "bn2.gamma"], bn2, self.g[pre + "bn2.gamma"], self.g[pre + "bn2.beta"],
+                                    *((self.p[pre + "res_bn.gamma"], rbn, self.g[pre + "res_bn.gamma"], self.g[pre + "res_bn.beta"])
+                                      if kind == "conv" else ()))
+            reduce(dY, y, u, r, bn2.mean, rmean, tail=tail)
+        else:
+            sums = reduce(dY, y, u, r, bn2.mean, rmean, mask=sb.get("ymask"))
+            self._bn_backward(pre + "bn2", sums, 4, 1, n_out)
+            if kind == "conv":
+                self._bn_backward(pre + "res_bn", sums, 4, 2, n_out)
 
     def _block_backward(self, i, sb, dY, B, gated=None, below=None):
         """gated: this block's BatchNorm-backward partial sums when dY already carries the ReLU gate (produced by the graph data
         gradient of the block above); below: the saved tensors of block i - 1 when THIS block's graph data gradient is to do the
-        same for it.  With the fused tail on (backward()) the return value is (dX, sums-for-the-block-below), else dX."""
-        fused_call = self._fuse_tail_f32()
+        same for it.  Returns (dX, sums-for-the-block-below or None)."""
         V, dev = self.V, dY.device
         pre = "l%d." % i
         X, g, u, r, y = sb["X"], sb["g"], sb["u"], sb["r"], sb["y"]
@@ -724,27 +742,8 @@ class STGCN:
         n_in, n_out = B * T * V, B * To * V
         bn1, bn2 = self.bn[pre + "bn1"], self.bn[pre + "bn2"]
         rbn = self.bn.get(pre + "res_bn")
-        # ---- tail: y = relu(bn2(u) + res)   (models/stgcn.py:37,62-63)
+        self._tail_backward_sums(pre, sb, dY, n_out, gated, ops.bn_add_relu_bwd_reduce)
         rk = (rbn.k1, rbn.k2, rbn.k3) if kind == "conv" else None
-        if gated is not None:    # the sums came with dY: (sum dz, sum dz (u - mean)) per channel and partial
-            assert kind != "conv"
-            ops.bn_bwd_finalize(gated[0], gated[1], gated[1] * 2, 2, 0, 1, f, n_out, self.p[pre + "bn2.gamma"], bn2.mean, bn2.rstd,
-                                self.g[pre + "bn2.gamma"], self.g[pre + "bn2.beta"], bn2.k1, bn2.k2, bn2.k3)
-        elif ops.BN_TAIL:      # the reduce kernel's last workgroup per channel finalises BN2 (and the residual BN): no launch between
-            tail = ops.make_bn_tail(dev, n_out, self.p[pre + "bn2.gamma"], bn2, self.g[pre + "bn2.gamma"], self.g[pre + "bn2.beta"],
-                                    *((self.p[pre + "res_bn.gamma"], rbn, self.g[pre + "res_bn.gamma"], self.g[pre + "res_bn.beta"])
-                                      if kind == "conv" else ()))
-            ops.bn_add_relu_bwd_reduce(dY, y, u, r if kind == "conv" else None, bn2.mean, rbn.mean if kind == "conv" else None,
-                                       tail=tail)
-        else:
-            part, nparts = ops.bn_add_relu_bwd_reduce(dY, y, u, r if kind == "conv" else None, bn2.mean,
-                                                      rbn.mean if kind == "conv" else None, mask=sb.get("ymask"))
-            ops.bn_bwd_finalize(part, nparts, nparts * 4, 4, 0, 1, f, n_out, self.p[pre + "bn2.gamma"], bn2.mean, bn2.rstd,
-                                self.g[pre + "bn2.gamma"], self.g[pre + "bn2.beta"], bn2.k1, bn2.k2, bn2.k3)
-            if kind == "conv":
-                ops.bn_bwd_finalize(part, nparts, nparts * 4, 4, 0, 2, f, n_out, self.p[pre + "res_bn.gamma"], rbn.mean,
-                                    rbn.rstd, self.g[pre + "res_bn.gamma"], self.g[pre + "res_bn.beta"], rbn.k1, rbn.k2,
-                                    rbn.k3)
         du = torch.empty_like(u)
         dr = torch.empty_like(r) if kind == "conv" else None
         dz = dY if (kind == "identity" and gated is None) else None  # in place: dY becomes the pre-ReLU gradient for the skip path (already gated: nothing to write)
@@ -773,14 +772,13 @@ class STGCN:
                            stride=s, pad=pad, transposed=True, epi=L.SAR_EPI_MASK, aux=g,
                            aux_affine=(bn1.scale, bn1.shift), aux_mean=bn1.mean,
                            **self._split_args(simg, self._cell(i, 1), wimg))
-        ops.bn_bwd_finalize(pm[0], pm[1], pm[1] * 2, 2, 0, 1, f, n_in, self.p[pre + "bn1.gamma"], bn1.mean, bn1.rstd,
-                            self.g[pre + "bn1.gamma"], self.g[pre + "bn1.beta"], bn1.k1, bn1.k2, bn1.k3)
+        self._bn_backward(pre + "bn1", pm, 2, 1, n_in)
         dg = dz1
         dgcell = self._cell(i, 2) if self._cell_live(pre + "gcn.b", "gdgrad", "gwgrad") else None      # the bound of dg: by-product
         ops.affine2(dz1, g, (bn1.k1, bn1.k2, bn1.k3), dg, amax_cell=dgcell)   # BN1 backward apply (in place)
         flat_g = self.grad[self.offsets[pre + "gcn.kernel"]:self.offsets[pre + "gcn.bias"] + KS * f]
         if self.dense_A:
-            return self._graph_backward_dense(i, sb, dg, dY, dr, B, flat_g)
+            return self._graph_backward_dense(i, sb, dg, dY, dr, B, flat_g), None
         # ---- graph conv: weight / bias gradient
         gw_split = self.split if ("gwgrad" in _SPLIT_KINDS and self._split_has(pre + "gcn.f")
                                   and self._split_has(pre + "gcn.b")) else None      # (both bounds exist: X from the forward, dg above)
@@ -809,7 +807,7 @@ class STGCN:
         ops.conv_gemm(L.SAR_CONV_GRAPH, dg, dX, gT, f * cin, cin, B=B, V=V, T_src=T, T_out=T, Kc=f, M=cin, taps=KS,
                       tables=self.tab_bwd, epi=L.SAR_EPI_ADD if aux is not None else L.SAR_EPI_NONE, aux=aux, aux_even_frames=even,
                       **self._split_args(sgimg, self._cell(i, 2), gimg))
-        return (dX, None) if fused_call else dX
+        return dX, None
 
     def _residual_backward(self, i, sb, dr, B):
         """weight gradient and data gradient of the strided 1x1 residual convolution (blocks 5 and 8); None otherwise"""
@@ -856,8 +854,7 @@ class STGCN:
         blocks of a split engine whose dense 1x1 product runs on conv_tap1_split_kernel (round 6)"""
         on = _COMPACT_SKIP == "1" or (_COMPACT_SKIP == "fp32" and (not self.split or (
             i is not None and self._simg("l%d.res.b" % i) is not None)))
-        return (on and s == 2 and not self.bf16 and not getattr(self, "cn8", False)
-                and not self.dense_A and type(self)._block_backward is STGCN._block_backward)
+        return on and s == 2 and not self.bf16 and not self.cn8 and not self.dense_A and self.stock_backward
 
     def _graph_backward_dense(self, i, sb, dg, dY, dr, B, flat_g):
         """Backward of Conv2D(3F, 1x1) -> einsum with the trainable adjacency (models/gcn.py:229-237): dy3 = dg . A^T per
@@ -895,7 +892,7 @@ class STGCN:
 
     def sgd_step(self, lr, momentum=0.9):
         """tf.keras SGD(momentum, nesterov=True) over the flat buffers (main_gnn.py:312-314)."""
-        if getattr(self, "_lr_host", None) != float(lr):      # one launch less per step while the schedule holds the rate
+        if self._lr_host != float(lr):      # one launch less per step while the schedule holds the rate
             self.lr_dev.fill_(float(lr))
             self._lr_host = float(lr)
         ops.sgd_nesterov(self.flat, self.velocity, self.grad, self.lr_dev, momentum)

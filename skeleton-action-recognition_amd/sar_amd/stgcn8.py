@@ -6,18 +6,24 @@ accumulators, parameters, gradients, optimizer state and the loss head are fp32.
 consumer's operand staging, the 3F-channel GraphConvTD intermediate never exists.
 
 These functions are the bodies of STGCN.forward / STGCN.backward when engine.cn8 is set."""
+import os
+
 import torch
 
 from . import _lib as L
 from . import ops, ops8
 from .stgcn import BN_EPS, BN_MOMENTUM, KS, KT, same_pad  # noqa: F401
 
-RELU_MASK = __import__("os").environ.get("SAR_CN8_RELU_MASK", "1") == "1"
+# training: the block tail also writes its ReLU mask, one BYTE per 16-byte unit; the two BatchNorm-backward passes read that instead
+# of y (SAR_CN8_RELU_MASK=0: they read y)
+RELU_MASK = os.environ.get("SAR_CN8_RELU_MASK", "1") == "1"
 # Round 4: the graph data gradient of block i gates its result (= the output gradient of block i - 1) with block i - 1's ReLU
 # mask and reduces block i - 1's BatchNorm-backward sums in its epilogue (SAR_EPI_ADD_GATE): block i - 1 then needs neither the
 # bn_add_relu_bwd_reduce pass nor the masked-gradient write of its apply pass.  Not for a block whose residual branch has its own
 # BatchNorm (a third sum over r) and not for the last block (its output gradient comes from the pooling).  SAR_CN8_FUSE_TAIL=0: off.
-FUSE_TAIL = __import__("os").environ.get("SAR_CN8_FUSE_TAIL", "1") == "1"
+FUSE_TAIL = os.environ.get("SAR_CN8_FUSE_TAIL", "1") == "1"
+# SAR_GRAPH_READ_GATHER=0: the matrix-core adjacency gather (conv_graph_cn8_kernel), whose epilogue has no gate: the tail stays unfused
+_READ_GATHER = os.environ.get("SAR_GRAPH_READ_GATHER", "1") != "0"
 
 
 def forward(eng, x, training=True, keep=None):
@@ -28,14 +34,11 @@ def forward(eng, x, training=True, keep=None):
     dev, B = x.device, N * M
     saved = {"x": x, "N": N, "M": M, "T": T, "blocks": [], "training": training}
     eng.packed.refresh(eng.flat)           # bf16 operand images of every conv weight, one launch
-    nch = V * Cin
+    part = None
     if training:
-        part = torch.empty((nch, N, 2), dtype=torch.float32, device=dev)
+        part = torch.empty((V * Cin, N, 2), dtype=torch.float32, device=dev)
         ops.data_bn_stats(x, eng.bone_parent, part, eng.motion)
-        eng._bn_forward_stats("data_bn", part, N, N * M * T, True, False)
-    else:
-        eng._bn_eval("data_bn")
-    dbn = eng.bn["data_bn"]
+    dbn = eng._bn_forward("data_bn", (part, N), N * M * T, training, unbiased=False)
     h = ops8.empty(Cin, B * T * V, dev)
     ops8.data_bn_apply(x, eng.bone_parent, dbn.scale, dbn.shift, h, eng.motion)
     if keep is not None:
@@ -66,33 +69,19 @@ def _block_forward(eng, i, X, cin, f, s, B, T, training, saved, keep):
     g = ops8.empty(f, n_in, dev)
     r1 = ops8.conv_gemm(L.SAR_CONV_GRAPH, X, g, img(pre + "gcn.f"), B=B, V=V, T_src=T, T_out=T, Kc=cin, M=f, taps=KS,
                         bias=eng.p[pre + "gcn.bias"], tables=eng.tab_fwd, epi=epi)
-    if training:
-        eng._bn_forward_stats(pre + "bn1", r1[0], r1[1], n_in, True, True)
-    else:
-        eng._bn_eval(pre + "bn1")
-    bn1 = eng.bn[pre + "bn1"]
+    bn1 = eng._bn_forward(pre + "bn1", r1, n_in, training)
     u = ops8.empty(f, n_out, dev)
     r2 = ops8.conv_gemm(L.SAR_CONV_TEMPORAL, g, u, img(pre + "tcn.f"), B=B, V=V, T_src=T, T_out=To, Kc=f, M=f, taps=KT, stride=s,
                         pad=pad, bias=eng.p[pre + "tcn.bias"], pro=(bn1.scale, bn1.shift), pro_relu=True, epi=epi)
-    if training:
-        eng._bn_forward_stats(pre + "bn2", r2[0], r2[1], n_out, True, True)
-    else:
-        eng._bn_eval(pre + "bn2")
-    bn2 = eng.bn[pre + "bn2"]
+    bn2 = eng._bn_forward(pre + "bn2", r2, n_out, training)
     r = rbn = None
     if kind == "conv":
         r = ops8.empty(f, n_out, dev)
         r3 = ops8.conv_gemm(L.SAR_CONV_TEMPORAL, X, r, img(pre + "res.f"), B=B, V=V, T_src=T, T_out=To, Kc=cin, M=f, taps=1,
                             stride=s, pad=0, bias=eng.p[pre + "res.bias"], epi=epi)
-        if training:
-            eng._bn_forward_stats(pre + "res_bn", r3[0], r3[1], n_out, True, True)
-        else:
-            eng._bn_eval(pre + "res_bn")
-        rbn = eng.bn[pre + "res_bn"]
+        rbn = eng._bn_forward(pre + "res_bn", r3, n_out, training)
     y = ops8.empty(f, n_out, dev)
     res_kind = {"none": 0, "identity": 1, "conv": 2}[kind]
-    # training: the tail also writes its ReLU mask, one BYTE per 16-byte unit; the two BatchNorm-backward passes read that
-    # instead of y (SAR_CN8_RELU_MASK=0: they read y)
     ymask = ops8.relu_mask(f, n_out, dev) if (training and RELU_MASK) else None
     ops8.bn_add_relu_fwd(u, bn2.scale, bn2.shift, res_kind, X if kind == "identity" else r, rbn.scale if rbn else None,
                          rbn.shift if rbn else None, y, f, mask=ymask)
@@ -117,7 +106,7 @@ def backward(eng, dlogits, bucket_cb=None):
     dY = ops8.empty(c_last, sv["y_last_shape"][1], dev)
     ops8.pool_bwd(dfeat, c_last, B, sv["T_last"] * V, M, dY)
     gated = None       # (partials, nparts) of this block's BatchNorm-backward sums when dY arrives gated from the block above
-    fuse = FUSE_TAIL and RELU_MASK and bool(eng.tab_bwd.g_flags & L.SAR_GRAPH_FEW_DENSE) and __import__("os").environ.get("SAR_GRAPH_READ_GATHER", "1") != "0"
+    fuse = FUSE_TAIL and RELU_MASK and bool(eng.tab_bwd.g_flags & L.SAR_GRAPH_FEW_DENSE) and _READ_GATHER
     for i in reversed(range(len(eng.blocks))):
         below = sv["blocks"][i - 1] if (fuse and i >= 1 and eng.kinds[i - 1] != "conv" and sv["blocks"][i - 1].get("ymask") is not None) else None
         dY, gated = _block_backward(eng, i, sv["blocks"][i], dY, B, gated, below)
@@ -128,10 +117,8 @@ def backward(eng, dlogits, bucket_cb=None):
     x = sv["x"]
     nch = V * eng.C_in
     part = torch.empty((nch, N, 2), dtype=torch.float32, device=dev)
-    dbn = eng.bn["data_bn"]
-    ops8.data_bn_bwd_reduce(x, eng.bone_parent, dY, dbn.mean, part, eng.motion)
-    ops.bn_bwd_finalize(part, N, N * 2, 2, 0, 1, nch, N * M * sv["T"], eng.p["data_bn.gamma"], dbn.mean, dbn.rstd,
-                        eng.g["data_bn.gamma"], eng.g["data_bn.beta"])
+    ops8.data_bn_bwd_reduce(x, eng.bone_parent, dY, eng.bn["data_bn"].mean, part, eng.motion)
+    eng._bn_backward("data_bn", (part, N), 2, 1, N * M * sv["T"], coefficients=False)
     eng._finish_backward(bucket_cb)
 
 
@@ -148,25 +135,10 @@ def _block_backward(eng, i, sb, dY, B, gated=None, below=None):
     rbn = eng.bn.get(pre + "res_bn")
     conv = kind == "conv"
     img = eng.packed.image
-    # ---- tail: y = relu(bn2(u) + res)
+    def reduce(dY, y, u, r, mu, mr, **kw):
+        return ops8.bn_add_relu_bwd_reduce(dY, y, u, r, f, mu, mr, **kw)
+    eng._tail_backward_sums(pre, sb, dY, n_out, gated, reduce)
     rk = (rbn.k1, rbn.k2, rbn.k3) if conv else None
-    if gated is not None:    # the sums came with dY: (sum dz, sum dz (u - mean)) per channel and partial
-        assert not conv
-        ops.bn_bwd_finalize(gated[0], gated[1], gated[1] * 2, 2, 0, 1, f, n_out, eng.p[pre + "bn2.gamma"], bn2.mean, bn2.rstd,
-                            eng.g[pre + "bn2.gamma"], eng.g[pre + "bn2.beta"], bn2.k1, bn2.k2, bn2.k3)
-    elif ops.BN_TAIL:          # the reduce kernel's last workgroup per plane finalises BN2 (and the residual BN): no launch between
-        tail = ops.make_bn_tail(dev, n_out, eng.p[pre + "bn2.gamma"], bn2, eng.g[pre + "bn2.gamma"], eng.g[pre + "bn2.beta"],
-                                *((eng.p[pre + "res_bn.gamma"], rbn, eng.g[pre + "res_bn.gamma"], eng.g[pre + "res_bn.beta"])
-                                  if conv else ()))
-        ops8.bn_add_relu_bwd_reduce(dY, y, u, r if conv else None, f, bn2.mean, rbn.mean if conv else None, tail=tail)
-    else:
-        part, nparts = ops8.bn_add_relu_bwd_reduce(dY, y, u, r if conv else None, f, bn2.mean, rbn.mean if conv else None,
-                                                   mask=sb.get("ymask"))
-        ops.bn_bwd_finalize(part, nparts, nparts * 4, 4, 0, 1, f, n_out, eng.p[pre + "bn2.gamma"], bn2.mean, bn2.rstd,
-                            eng.g[pre + "bn2.gamma"], eng.g[pre + "bn2.beta"], bn2.k1, bn2.k2, bn2.k3)
-        if conv:
-            ops.bn_bwd_finalize(part, nparts, nparts * 4, 4, 0, 2, f, n_out, eng.p[pre + "res_bn.gamma"], rbn.mean, rbn.rstd,
-                                eng.g[pre + "res_bn.gamma"], eng.g[pre + "res_bn.beta"], rbn.k1, rbn.k2, rbn.k3)
     du = ops8.empty(f, n_out, dev)
     dr = ops8.empty(f, n_out, dev) if conv else None
     dz = dY if (kind == "identity" and gated is None) else None      # in place: dY becomes the pre-ReLU gradient for the skip path (already gated: nothing to write)
@@ -180,8 +152,7 @@ def _block_backward(eng, i, sb, dY, B, gated=None, below=None):
     pm = ops8.conv_gemm(L.SAR_CONV_TEMPORAL, du, dz1, img(pre + "tcn.b"), B=B, V=V, T_src=To, T_out=T, Kc=f, M=f, taps=KT,
                         stride=s, pad=pad, transposed=True, epi=L.SAR_EPI_MASK, aux=g, aux_affine=(bn1.scale, bn1.shift),
                         aux_mean=bn1.mean)
-    ops.bn_bwd_finalize(pm[0], pm[1], pm[1] * 2, 2, 0, 1, f, n_in, eng.p[pre + "bn1.gamma"], bn1.mean, bn1.rstd,
-                        eng.g[pre + "bn1.gamma"], eng.g[pre + "bn1.beta"], bn1.k1, bn1.k2, bn1.k3)
+    eng._bn_backward(pre + "bn1", pm, 2, 1, n_in)
     dg = dz1
     ops8.affine2(dz1, g, (bn1.k1, bn1.k2, bn1.k3), dg, f)             # BN1 backward apply (in place)
     # ---- graph conv: weight / bias gradient

@@ -28,6 +28,8 @@ def block_frames(frames, blocks):
 
 
 class STGCNTA(STGCN):
+    env_arithmetic = third_stream = False      # fp32, nothing to fork: no third stream (sar_amd/stgcn.py)
+
     def __init__(self, num_classes=60, in_channels=3, num_node=25, A=None, device="cuda", seed=0, bone_pairs=None, blocks=None,
                  motion=False, mfma="fp32", trainable_adjacency=True, frames=300):
         assert mfma == "fp32", "the per-frame adjacency engine is fp32"

@@ -22,111 +22,66 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .stgcn import STGCN, _BN, BLOCKS, KS, KT, same_pad, ntu_adjacency
+from .stgcn import STGCN, _BN, BLOCKS, KS, KT, same_pad, ntu_adjacency  # noqa: F401 (BLOCKS: models/stgin.py)
 
 
 class STGIN(STGCN):
+    # fp32 with its own block backward: per-gradient slab reductions, no third stream, one ops.transpose per data-gradient operand
+    env_arithmetic = batched_slabs = third_stream = batched_wT = stock_backward = False
+
     def __init__(self, num_classes=60, in_channels=3, num_node=25, A=None, device="cuda", seed=0, bone_pairs=None,
                  blocks=None, motion=False, mfma="fp32"):
-        L.load()  # fail loudly if the HIP library is missing
         assert mfma == "fp32", "the ST-GIN engine is fp32"
-        import os
-        self.cn8 = self.bf16 = self.dense_A = False
+        super().__init__(num_classes=num_classes, in_channels=in_channels, num_node=num_node, A=A, device=device, seed=seed,
+                         bone_pairs=bone_pairs, blocks=blocks, motion=motion, mfma="fp32")
         self.train_adjacency = False
-        self.packed = None
-        self._wT_off, self._wT_perm, self._wT = {}, None, None      # STGCN's batched data-gradient operands: not used here
-        self.device = torch.device(device)
-        self.num_classes, self.C_in, self.V = num_classes, in_channels, num_node
-        self.blocks = list(blocks if blocks is not None else BLOCKS)
+        self._zeros = torch.zeros(max([in_channels] + [f for f, s, res in self.blocks]), dtype=torch.float32, device=self.device)
+
+    # ------------------------------------------------------------------ the constructor's steps that differ from STGCN's
+    def _init_adjacency(self, A):
         A = np.asarray(ntu_adjacency()[:KS - 1] if A is None else A, dtype=np.float64)       # models/stgin.py:87-90: Graph().A[:2]
-        assert A.shape == (KS - 1, num_node, num_node)
+        assert A.shape == (KS - 1, self.V, self.V)
         self.A_host = A.astype(np.float32)
         self.A = torch.from_numpy(self.A_host).to(self.device).contiguous()    # 'adjacency_matrix', non-trainable
         # The adjacency is fixed, so the contractions x . A_k run as <= 4-entry gathers (sar_graph_gather_*_f32) when every
         # column / row of [A_0, .., diag(1)] has <= 4 non-zeros (the NTU graph); a slice that IS the identity (slice 0 of the
         # 'spatial' strategy) is not materialised at all.  Denser adjacencies take the dense kernels (csrc/graph_dense.hip).
-        a_ext = np.concatenate([self.A_host, np.eye(num_node, dtype=np.float32)[None]])
+        eye = np.eye(self.V, dtype=np.float32)
+        a_ext = np.concatenate([self.A_host, eye[None]])
         try:
             self.tab_f = ops.GraphTables(a_ext, self.device, transpose=False)
             self.tab_b = ops.GraphTables(a_ext, self.device, transpose=True)
-            self.identity_slice = [bool(np.array_equal(self.A_host[k], np.eye(num_node, dtype=np.float32))) for k in range(KS - 1)]
+            self.identity_slice = [bool(np.array_equal(self.A_host[k], eye)) for k in range(KS - 1)]
         except ValueError:
             self.tab_f = self.tab_b = None
             self.identity_slice = [False] * (KS - 1)
-        self._side = (ops.shared_side_stream(self.device, int(os.environ.get("SAR_WGRAD_PRIO", "0")))
-                      if self.device.type == "cuda" and os.environ.get("SAR_WGRAD_STREAM", "1") == "1" else None)
-        self.motion = bool(motion)
-        self.bone_parent = None
-        if bone_pairs is not None:
-            bp = np.full(num_node, -1, dtype=np.int32)
-            for v1, v2 in bone_pairs:
-                bp[v1 - 1] = v2 - 1
-            self.bone_parent = torch.from_numpy(bp).to(self.device)
 
-        # ---- parameter table (Keras layouts).  Branch parameters of one kind are registered back to back so that the
-        # stacked [K*h] views used by the kernels are contiguous ranges of the flat buffer (h % 4 == 0).
-        self.shapes = {}
-        nch = num_node * in_channels
-        self._add("data_bn.gamma", (nch,)), self._add("data_bn.beta", (nch,))
-        cin = in_channels
-        self.kinds = []
-        for i, (f, s, res) in enumerate(self.blocks):
-            pre, h = "l%d." % i, f // 2
-            assert f % 8 == 0, "filters / 2 must be a multiple of 4"
-            self.kinds.append("none" if not res else ("identity" if (cin == f and s == 1) else "conv"))   # stgin.py:41-56
-            for k in range(KS):
-                self._add(pre + "mlp%d.c1.kernel" % k, (1, 1, cin, h)), self._add(pre + "mlp%d.c1.bias" % k, (h,))
-            for k in range(KS):
-                self._add(pre + "mlp%d.c2.kernel" % k, (1, 1, h, h)), self._add(pre + "mlp%d.c2.bias" % k, (h,))
-            for bn in ("bn1", "bn2"):
-                for part in ("gamma", "beta"):
-                    for k in range(KS):
-                        self._add(pre + "mlp%d.%s.%s" % (k, bn, part), (h,))
-            self._add(pre + "epsilon", ())
-            self._add(pre + "bn1.gamma", (h,)), self._add(pre + "bn1.beta", (h,))
-            self._add(pre + "tcn.kernel", (KT, 1, h, f)), self._add(pre + "tcn.bias", (f,))
-            self._add(pre + "bn2.gamma", (f,)), self._add(pre + "bn2.beta", (f,))
-            if self.kinds[i] == "conv":
-                self._add(pre + "res.kernel", (1, 1, cin, f)), self._add(pre + "res.bias", (f,))
-                self._add(pre + "res_bn.gamma", (f,)), self._add(pre + "res_bn.beta", (f,))
-            cin = f
-        self.C_last = cin
-        self._add("logits.kernel", (1, 1, cin, num_classes)), self._add("logits.bias", (num_classes,))
-        total, self.offsets = 0, {}
-        for k, shp in self.shapes.items():
-            n = int(np.prod(shp))
-            if k.endswith(".kernel"):
-                assert n % 4 == 0, k
-            self.offsets[k] = total
-            total += n if k.endswith(".kernel") else (n + 3) // 4 * 4
-        self.n_params = sum(int(np.prod(shp)) for shp in self.shapes.values())
-        dev = self.device
-        self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.velocity = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.lr_dev = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.p = {k: self._view(self.flat, k) for k in self.shapes}
-        self.g = {k: self._view(self.grad, k) for k in self.shapes}
-        self.bn = {"data_bn": _BN(nch, dev)}
-        cmax = in_channels
-        for i, (f, s, res) in enumerate(self.blocks):
-            pre, h = "l%d." % i, f // 2
-            for bn in ("bn1", "bn2"):      # stacked views / state of the K branch BatchNorms
-                for part in ("gamma", "beta"):
-                    o = self.offsets[pre + "mlp0.%s.%s" % (bn, part)]
-                    assert self.offsets[pre + "mlp%d.%s.%s" % (KS - 1, bn, part)] == o + (KS - 1) * h
-                    self.p[pre + "mlp.%s.%s" % (bn, part)] = self.flat[o:o + KS * h]
-                    self.g[pre + "mlp.%s.%s" % (bn, part)] = self.grad[o:o + KS * h]
-                self.bn[pre + "mlp." + bn] = _BN(KS * h, dev)
-            self.bn[pre + "bn1"], self.bn[pre + "bn2"] = _BN(h, dev), _BN(f, dev)
-            if self.kinds[i] == "conv":
-                self.bn[pre + "res_bn"] = _BN(f, dev)
-            cmax = max(cmax, f)
-        self._zeros = torch.zeros(cmax, dtype=torch.float32, device=dev)
-        self._init_params(seed)
-        self._saved = None
-        self._deferred, self._flushing = [], False
-        self._buckets = self._make_buckets(total)
+    def _declare_block(self, pre, cin, f, kind):
+        """Branch parameters of one kind are registered back to back so that the stacked [K*h] views used by the kernels are
+        contiguous ranges of the flat buffer (h % 4 == 0)."""
+        h = f // 2
+        assert f % 8 == 0, "filters / 2 must be a multiple of 4"
+        for k in range(KS):
+            self._add(pre + "mlp%d.c1.kernel" % k, (1, 1, cin, h)), self._add(pre + "mlp%d.c1.bias" % k, (h,))
+        for k in range(KS):
+            self._add(pre + "mlp%d.c2.kernel" % k, (1, 1, h, h)), self._add(pre + "mlp%d.c2.bias" % k, (h,))
+        for bn in ("bn1", "bn2"):
+            for part in ("gamma", "beta"):
+                for k in range(KS):
+                    self._add(pre + "mlp%d.%s.%s" % (k, bn, part), (h,))
+        self._add(pre + "epsilon", ())
+        self._declare_temporal(pre, h, cin, f, kind)
+
+    def _init_block_bn(self, pre, f, kind):
+        h = f // 2
+        for bn in ("bn1", "bn2"):      # stacked views / state of the K branch BatchNorms
+            for part in ("gamma", "beta"):
+                o = self.offsets[pre + "mlp0.%s.%s" % (bn, part)]
+                assert self.offsets[pre + "mlp%d.%s.%s" % (KS - 1, bn, part)] == o + (KS - 1) * h
+                self.p[pre + "mlp.%s.%s" % (bn, part)] = self.flat[o:o + KS * h]
+                self.g[pre + "mlp.%s.%s" % (bn, part)] = self.grad[o:o + KS * h]
+            self.bn[pre + "mlp." + bn] = _BN(KS * h, self.device)
+        super()._init_block_bn(pre, f, kind, c=h)
 
     # ------------------------------------------------------------------ parameters
     @staticmethod
@@ -197,7 +152,7 @@ class STGIN(STGCN):
             src = [z[k * cin:(k + 1) * cin] for k in range(K - 1)] + [X]
         a1, a2 = new(K * h, n_in), new(K * h, n_in)
         geo = dict(B=B, V=V, T_src=T, T_out=T, taps=1, stride=1, pad=0)
-        part1 = part2 = None
+        part1 = part2 = np1 = np2 = None
         if training:
             np1 = ops.conv_gemm_nparts(Kc=cin, M=h, **geo)
             np2 = ops.conv_gemm_nparts(Kc=h, M=h, **geo)
@@ -208,47 +163,27 @@ class STGIN(STGCN):
             ops.conv_gemm(L.SAR_CONV_TEMPORAL, src[k], rows(a1, k), self.p[pre + "mlp%d.c1.kernel" % k], 0, h, Kc=cin, M=h,
                           bias=self.p[pre + "mlp%d.c1.bias" % k], pro=(escale, self._zeros[:cin]) if k == K - 1 else None,
                           epi=epi, partials_out=rows(part1, k), **geo)
-        m1 = self.bn[pre + "mlp.bn1"]
-        if training:
-            self._bn_forward_stats(pre + "mlp.bn1", part1, np1, n_in, True, True)
-        else:
-            self._bn_eval(pre + "mlp.bn1")
+        m1 = self._bn_forward(pre + "mlp.bn1", (part1, np1), n_in, training)
         for k in range(K):
             ops.conv_gemm(L.SAR_CONV_TEMPORAL, rows(a1, k), rows(a2, k), self.p[pre + "mlp%d.c2.kernel" % k], 0, h, Kc=h, M=h,
                           bias=self.p[pre + "mlp%d.c2.bias" % k], pro=(rows(m1.scale, k), rows(m1.shift, k)), pro_relu=True,
                           epi=epi, partials_out=rows(part2, k), **geo)
-        m2 = self.bn[pre + "mlp.bn2"]
-        if training:
-            self._bn_forward_stats(pre + "mlp.bn2", part2, np2, n_in, True, True)
-        else:
-            self._bn_eval(pre + "mlp.bn2")
+        m2 = self._bn_forward(pre + "mlp.bn2", (part2, np2), n_in, training)
         g = new(h, n_in)
         r1 = ops.gin_sum_fwd(a2, m2.scale, m2.shift, K, g, stats=training)
-        if training:
-            self._bn_forward_stats(pre + "bn1", r1[0], r1[1], n_in, True, True)
-        else:
-            self._bn_eval(pre + "bn1")
-        bn1 = self.bn[pre + "bn1"]
+        bn1 = self._bn_forward(pre + "bn1", r1, n_in, training)
         # ---- tgcn (models/stgin.py:27-39), residual (:41-56), ReLU
         u = new(f, n_out)
         r2 = ops.conv_gemm(L.SAR_CONV_TEMPORAL, g, u, self.p[pre + "tcn.kernel"], h * f, f, B=B, V=V, T_src=T, T_out=To, Kc=h,
                            M=f, taps=KT, stride=s, pad=pad, bias=self.p[pre + "tcn.bias"], pro=(bn1.scale, bn1.shift),
                            pro_relu=True, epi=epi)
-        if training:
-            self._bn_forward_stats(pre + "bn2", r2[0], r2[1], n_out, True, True)
-        else:
-            self._bn_eval(pre + "bn2")
-        bn2 = self.bn[pre + "bn2"]
+        bn2 = self._bn_forward(pre + "bn2", r2, n_out, training)
         r = rbn = None
         if kind == "conv":
             r = new(f, n_out)
             r3 = ops.conv_gemm(L.SAR_CONV_TEMPORAL, X, r, self.p[pre + "res.kernel"], 0, f, B=B, V=V, T_src=T, T_out=To, Kc=cin,
                                M=f, taps=1, stride=s, pad=0, bias=self.p[pre + "res.bias"], epi=epi)
-            if training:
-                self._bn_forward_stats(pre + "res_bn", r3[0], r3[1], n_out, True, True)
-            else:
-                self._bn_eval(pre + "res_bn")
-            rbn = self.bn[pre + "res_bn"]
+            rbn = self._bn_forward(pre + "res_bn", r3, n_out, training)
         y = new(f, n_out)
         ops.bn_add_relu_fwd(u, bn2.scale, bn2.shift, {"none": 0, "identity": 1, "conv": 2}[kind], X if kind == "identity" else r,
                             rbn.scale if rbn else None, rbn.shift if rbn else None, y)
@@ -260,7 +195,8 @@ class STGIN(STGCN):
         return y, To
 
     # ------------------------------------------------------------------ backward
-    def _block_backward(self, i, sb, dY, B):
+    def _block_backward(self, i, sb, dY, B, gated=None, below=None):
+        """Returns (dX, None): no sums for the block below (STGCN._block_backward)"""
         V, dev = self.V, dY.device
         pre, K = "l%d." % i, KS
         X, g, u, r, y, src, a1, a2 = sb["X"], sb["g"], sb["u"], sb["r"], sb["y"], sb["src"], sb["a1"], sb["a2"]
@@ -271,22 +207,8 @@ class STGIN(STGCN):
         rbn = self.bn.get(pre + "res_bn")
         new = lambda rows, n: torch.empty((rows, n), dtype=torch.float32, device=dev)
         rows = lambda t, k: t[k * h:(k + 1) * h]
-        # ---- tail: y = relu(bn2(u) + res)
+        self._tail_backward_sums(pre, sb, dY, n_out, None, ops.bn_add_relu_bwd_reduce)
         rk = (rbn.k1, rbn.k2, rbn.k3) if kind == "conv" else None
-        if ops.BN_TAIL:      # the reduce kernel's last workgroup per channel finalises BN2 (and the residual BN)
-            tail = ops.make_bn_tail(dev, n_out, self.p[pre + "bn2.gamma"], bn2, self.g[pre + "bn2.gamma"], self.g[pre + "bn2.beta"],
-                                    *((self.p[pre + "res_bn.gamma"], rbn, self.g[pre + "res_bn.gamma"], self.g[pre + "res_bn.beta"])
-                                      if kind == "conv" else ()))
-            ops.bn_add_relu_bwd_reduce(dY, y, u, r if kind == "conv" else None, bn2.mean, rbn.mean if kind == "conv" else None,
-                                       tail=tail)
-        else:
-            part, nparts = ops.bn_add_relu_bwd_reduce(dY, y, u, r if kind == "conv" else None, bn2.mean,
-                                                      rbn.mean if kind == "conv" else None)
-            ops.bn_bwd_finalize(part, nparts, nparts * 4, 4, 0, 1, f, n_out, self.p[pre + "bn2.gamma"], bn2.mean, bn2.rstd,
-                                self.g[pre + "bn2.gamma"], self.g[pre + "bn2.beta"], bn2.k1, bn2.k2, bn2.k3)
-            if kind == "conv":
-                ops.bn_bwd_finalize(part, nparts, nparts * 4, 4, 0, 2, f, n_out, self.p[pre + "res_bn.gamma"], rbn.mean, rbn.rstd,
-                                    self.g[pre + "res_bn.gamma"], self.g[pre + "res_bn.beta"], rbn.k1, rbn.k2, rbn.k3)
         du = torch.empty_like(u)
         dr = torch.empty_like(r) if kind == "conv" else None
         dz = dY if kind == "identity" else None
@@ -302,13 +224,10 @@ class STGIN(STGCN):
         pm = ops.conv_gemm(L.SAR_CONV_TEMPORAL, du, ds, wT, f * h, h, B=B, V=V, T_src=To, T_out=T, Kc=f, M=h, taps=KT, stride=s,
                            pad=pad, transposed=True, epi=L.SAR_EPI_MASK, aux=g, aux_affine=(bn1.scale, bn1.shift),
                            aux_mean=bn1.mean)
-        ops.bn_bwd_finalize(pm[0], pm[1], pm[1] * 2, 2, 0, 1, h, n_in, self.p[pre + "bn1.gamma"], bn1.mean, bn1.rstd,
-                            self.g[pre + "bn1.gamma"], self.g[pre + "bn1.beta"], bn1.k1, bn1.k2, bn1.k3)
+        self._bn_backward(pre + "bn1", pm, 2, 1, n_in)
         ops.affine2(ds, g, (bn1.k1, bn1.k2, bn1.k3), ds)                      # gradient w.r.t. s = sum of the branches
         # ---- branches, last BN + ReLU (all K in one launch each)
-        part, nparts = ops.gin_bwd_reduce(ds, a2, m2.scale, m2.shift, m2.mean, K)
-        ops.bn_bwd_finalize(part, nparts, nparts * 2, 2, 0, 1, K * h, n_in, self.p[pre + "mlp.bn2.gamma"], m2.mean, m2.rstd,
-                            self.g[pre + "mlp.bn2.gamma"], self.g[pre + "mlp.bn2.beta"], m2.k1, m2.k2, m2.k3)
+        self._bn_backward(pre + "mlp.bn2", ops.gin_bwd_reduce(ds, a2, m2.scale, m2.shift, m2.mean, K), 2, 1, n_in)
         da2 = a2                                                               # in place: a2 is not read again
         ops.gin_bwd_apply(ds, a2, m2.scale, m2.shift, (m2.k1, m2.k2, m2.k3), K, da2)
         # ---- second 1x1 convolution of every branch
@@ -327,8 +246,7 @@ class STGIN(STGCN):
             ops.conv_gemm(L.SAR_CONV_TEMPORAL, rows(da2, k), rows(da1, k), w2T[k], 0, h, Kc=h, M=h, transposed=True,
                           epi=L.SAR_EPI_MASK, aux=rows(a1, k), aux_affine=(rows(m1.scale, k), rows(m1.shift, k)),
                           aux_mean=rows(m1.mean, k), partials_out=rows(pm1, k), **geo)
-        ops.bn_bwd_finalize(pm1, npm, npm * 2, 2, 0, 1, K * h, n_in, self.p[pre + "mlp.bn1.gamma"], m1.mean, m1.rstd,
-                            self.g[pre + "mlp.bn1.gamma"], self.g[pre + "mlp.bn1.beta"], m1.k1, m1.k2, m1.k3)
+        self._bn_backward(pre + "mlp.bn1", (pm1, npm), 2, 1, n_in)
         ops.affine2(da1, a1, (m1.k1, m1.k2, m1.k3), da1)
         # ---- first 1x1 convolution of every branch; the self slice also yields d epsilon
         dzz = new(K * cin, n_in)
@@ -354,4 +272,4 @@ class STGIN(STGCN):
             ops.graph_gather_sum(dzz, self.tab_b, sb["sscale"], K, cin, V, dX, add=aux)
         else:
             ops.graph_dense_fwd(dzz, sb["table"], dX, K, cin, V, B * T, add=aux)
-        return dX
+        return dX, None

@@ -30,6 +30,8 @@ def glorot_uniform(shape, gen):
 
 
 class STPGCN(STGCN):
+    env_arithmetic = third_stream = False      # fp32, nothing to fork: no third stream (sar_amd/stgcn.py)
+
     def __init__(self, num_classes=60, in_channels=3, num_node=25, A=None, device="cuda", seed=0, bone_pairs=None, blocks=None,
                  motion=False, mfma="fp32", trainable_adjacency=False):
         assert mfma == "fp32", "the ST-PGCN engine is fp32"

@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Run-to-run determinism of the whole train step at the bench size: the kernels use no atomics and every reduction has
 a fixed order, so logits, loss and every gradient must be BITWISE identical between repetitions -- a mismatch means a
-race (LDS hazard, missing barrier).  Usage: python tools/determinism_check.py [--reps 5] [--batch 64]"""
+race (LDS hazard, missing barrier).  Usage: python tools/determinism_check.py [--reps 5] [--batch 64]
+
+--digest prints, per mode, the SHA-256 of logits, loss, grad and flat after each of two loss_and_grad + sgd_step rounds and of
+predict(x): two commits that print the same lines on the same machine and library compute the same steps."""
 import argparse
+import hashlib
 import os
 import sys
 
@@ -16,11 +20,28 @@ from sar_amd.stgcn import STGCN  # noqa: E402
 from sar_amd.train import synthetic_clips  # noqa: E402
 
 
+def sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def digest(mode, eng, x, y):
+    for step in range(2):
+        logits, loss = eng.loss_and_grad(x, y)[:2]
+        eng.sgd_step(0.1)
+        torch.cuda.synchronize()
+        for name, t in (("logits", logits), ("loss", loss), ("grad", eng.grad), ("flat", eng.flat)):
+            print("%s step%d %s %s" % (mode, step, name, sha(t)))
+    probs = eng.predict(x)
+    torch.cuda.synchronize()
+    print("%s predict %s" % (mode, sha(probs)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--modes", default="fp32,bf16")
+    ap.add_argument("--digest", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     total_bad = 0
@@ -35,6 +56,11 @@ def main():
             from sar_amd.stgin import STGIN
             eng = STGIN(num_classes=60, device=dev, seed=0)
             x, y = synthetic_clips(a.batch, dev, seed=3, num_classes=60)
+        elif mode in ("stpgcn", "stgcn_ta"):      # the sibling engines (fp32): the layer between two blocks / per-frame adjacencies
+            from sar_amd.stgcn_ta import STGCNTA
+            from sar_amd.stpgcn import STPGCN
+            eng = (STPGCN if mode == "stpgcn" else STGCNTA)(num_classes=60, device=dev, seed=0)
+            x, y = synthetic_clips(a.batch, dev, seed=3, num_classes=60)
         elif mode in ("dense", "bone_motion"):     # trainable adjacency (dense contraction kernels) / bone + motion input streams
             from sar_amd.bone import NTU_BONE_PAIRS
             kw = dict(trainable_adjacency=True) if mode == "dense" else dict(bone_pairs=NTU_BONE_PAIRS, motion=True)
@@ -43,6 +69,9 @@ def main():
         else:
             eng = STGCN(num_classes=60, device=dev, seed=0, mfma=mode)
             x, y = synthetic_clips(a.batch, dev, seed=3, num_classes=60)
+        if a.digest:
+            digest(mode, eng, x, y)
+            continue
         state = {k: v.clone() for k, v in eng.state_dict().items()}
         ref = None
         for r in range(a.reps):
