@@ -618,6 +618,25 @@ int sar_graph_dense_t_dadj_f32(const float* y, int64_t ld_y, const float* dout, 
                                int T, float* slab, float* dAt, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * Adjacency that depends on the SAMPLE (models/gcn.py:22-36 GraphConv: Conv1D(filters, 1) then einsum 'ncv,nvw->ncw', the layer
+ * the projection models put behind their pooling step): A is [N][V][V] contiguous, activations fp32 CN [F][ld] with column
+ * n*V + v.  csrc/graph_sample.hip (fp32 MFMA, fp32 accumulation): 1 <= V <= 512 (larger: SAR_E_UNSUP), any F >= 1 and N >= 1 with
+ * N*V < 2^31; every ld >= N*V, no alignment beyond the element (as sar_graph_dense_*); columns past N*V are neither read nor
+ * written.  Every limit is checked before anything is launched.
+ * ------------------------------------------------------------------------------------------------ */
+/* models/gcn.py:22-36 (the einsum of GraphConv.call):  out[m, (n,w)] = sum_v y[m, (n,v)] * A[n, v, w] */
+int sar_graph_sample_fwd_f32(const float* y, int64_t ld_y, const float* A, float* out, int64_t ld_out, int F, int V, int N,
+                             sar_stream_t s);
+/* models/gcn.py:22-36, the gradient of that einsum in its first operand:  dy[m, (n,v)] = sum_w dout[m, (n,w)] * A[n, v, w] */
+int sar_graph_sample_bwd_data_f32(const float* dout, int64_t ld_dout, const float* A, float* dy, int64_t ld_dy, int F, int V, int N,
+                                  sar_stream_t s);
+/* models/gcn.py:22-36, the gradient in the adjacency:  dA[n, v, w] = sum_m y[m, (n,v)] * dout[m, (n,w)]  (dA [N][V][V] contiguous;
+ * no reduction over samples, so no scratch).  All three: a sample's result does not depend on the other samples, no atomics,
+ * repeated launches are bitwise equal. */
+int sar_graph_sample_dadj_f32(const float* y, int64_t ld_y, const float* dout, int64_t ld_dout, float* dA, int F, int V, int N,
+                              sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * Graph isomorphism convolution, SURVEY.md 8(f)-4 (models/gcn.py:112-163 GraphIsoConvTD as used by models/stgin.py:24-25):
  * fp32 CN layout; the K branch MLPs of a layer are stacked along the channel axis (row k*C + c).
  *   sar_gin_adjacency_f32   table[k][a][b] = A[k][b][a] (k < Km1), table[Km1] = (1 + eps[0]) I  -- models/gcn.py:150-153

@@ -7,10 +7,19 @@ reference's attribute names used by its training script (main_gnn.py:228-232,311
   * `trainable_variables` -- objects with a `.name`; the adjacency is exposed as the NON-trainable
     variable `adjacency_matrix` (models/stgcn.py:105-109),
   * block hyper-parameters (models/stgcn.py:113-123) are fixed as in the reference.
+
+`SpatioTemporalGraphConv` (models/stgcn.py:11-64) is the block as a layer of its own, for bodies that are not pre-built: one
+autograd node whose forward and backward are the ENGINE's block code (STGCN.block_forward / block_backward on a one-block engine:
+the folded BN + ReLU prologue of the temporal convolution, the statistics epilogues, bn_add_relu with the 1-bit mask and the matching
+backward passes).  It converts NCHW <-> CN at its boundary and copies its parameters into the engine per call, so a network composed
+of these layers pays that per layer where `Model` does not: an interface, not the fast path.
 """
+import numpy as np
 import torch
 
-from sar_amd.stgcn import STGCN, BLOCKS  # noqa: F401
+from models.gcn import GraphConvTD, _require, from_cn, to_cn, variance_scaling_
+from sar_amd.graph_tables import gather_lists
+from sar_amd.stgcn import STGCN, BLOCKS, KS, KT  # noqa: F401
 
 
 class _STGCNFunction(torch.autograd.Function):
@@ -88,3 +97,161 @@ class Model(torch.nn.Module):
         logits, loss = self.engine.loss_and_grad(x, labels, global_batch_size)
         self.engine.sgd_step(lr, momentum)
         return logits, loss
+
+
+class _BlockFunction(torch.autograd.Function):
+    """one ST-GCN block on the engine's block forward / backward (one autograd node)"""
+
+    @staticmethod
+    def forward(ctx, x, A, layer, eng, *params):
+        B, C, T, V = x.shape
+        y, To, sb = eng.block_forward(0, to_cn(x), B, T, True)
+        ctx.layer, ctx.eng, ctx.sb, ctx.call, ctx.shape = layer, eng, sb, layer._calls, (B, C, T, V)
+        return from_cn(y, (B, y.shape[0], To, V))
+
+    @staticmethod
+    def backward(ctx, dout):
+        layer, eng = ctx.layer, ctx.eng
+        if ctx.call != layer._calls:
+            raise RuntimeError("SpatioTemporalGraphConv was called again (training or inference: either overwrites the block's "
+                               "BatchNorm state) before this call's backward; use one layer instance per position and run "
+                               "evaluation calls after backward")
+        dX = eng.block_backward(0, ctx.sb, to_cn(dout.contiguous()), ctx.shape[0])
+        dA = eng.g["adjacency_matrix"].clone() if (eng.dense_A and ctx.needs_input_grad[1]) else None
+        grads = tuple(eng.g[k].clone() for k in layer._engine_names())
+        return ((from_cn(dX, ctx.shape) if ctx.needs_input_grad[0] else None), dA, None, None) + grads
+
+
+class SpatioTemporalGraphConv(torch.nn.Module):
+    """models/stgcn.py:11-64: GraphConvTD -> BN -> ReLU -> Conv2D([9, 1], stride) -> BN, plus the residual (none / identity / strided
+    1x1 convolution + BN, decided on the first call), add, ReLU.  forward(x (B,C,T,V), A (3,V,V), training) -> (x (B,filters,T/s,V), A).
+    Parameters in the Keras layouts: sgcn.kernel / sgcn.bias (the GraphConvTD it owns), bn1_*, tcn_kernel (9, 1, f, f) / tcn_bias, bn2_*,
+    res_kernel (1, 1, C, f) / res_bias / res_bn_*; moving statistics are buffers with the engine's eps, momentum and unbiased moving
+    variance.  training=False uses the moving statistics and updates nothing.  A that requires a gradient (or is denser than 4
+    non-zeros per column / row) takes the engine's dense path, which yields dA (V <= 32).
+    The engine behind the layer keeps ONE set of BatchNorm scales, shifts and batch statistics, which backward reads: any later call
+    of the same instance -- a training=False call included, since inference overwrites the folded scale and shift -- before a
+    training call's backward makes that backward raise RuntimeError."""
+
+    def __init__(self, filters, kernel_size=(3, 9), stride=1, activation="relu", residual=True):
+        super().__init__()
+        if activation != "relu":
+            raise ValueError("activation %r is not implemented (only 'relu' is)" % (activation,))
+        if tuple(kernel_size) != (KS, KT):
+            raise ValueError("kernel_size %r is not built (only [%d, %d] is)" % (kernel_size, KS, KT))
+        self.filters, self.stride, self.residual = int(filters), int(stride), bool(residual)
+        self.sgcn = GraphConvTD(filters, kernel_size=KS)
+        self.kind = None
+        self._engines, self._tables_of, self._calls = {}, None, 0
+
+    # ---- parameters (created on the first call, or by load_state_dict)
+    def _bn(self, name, C, device):
+        self.register_parameter(name + "_gamma", torch.nn.Parameter(torch.ones(C, dtype=torch.float32, device=device)))
+        self.register_parameter(name + "_beta", torch.nn.Parameter(torch.zeros(C, dtype=torch.float32, device=device)))
+        self.register_buffer(name + "_moving_mean", torch.zeros(C, dtype=torch.float32, device=device))
+        self.register_buffer(name + "_moving_var", torch.ones(C, dtype=torch.float32, device=device))
+
+    def _conv(self, name, shape, device):
+        k = torch.nn.Parameter(torch.empty(shape, dtype=torch.float32, device=device))
+        variance_scaling_(k)
+        self.register_parameter(name + "_kernel", k)
+        self.register_parameter(name + "_bias", torch.nn.Parameter(torch.zeros(shape[-1], dtype=torch.float32, device=device)))
+
+    def build(self, in_channels, device, kind=None):
+        if self.kind is not None:
+            if self.sgcn.kernel.shape[-2] != in_channels:
+                raise ValueError("the block was built for %d input channels, got %d" % (self.sgcn.kernel.shape[-2], in_channels))
+            return
+        f = self.filters
+        self.cin = int(in_channels)
+        # models/stgcn.py:41-56
+        self.kind = kind or ("none" if not self.residual else ("identity" if (in_channels == f and self.stride == 1) else "conv"))
+        self.sgcn.build(in_channels, device)
+        self._bn("bn1", f, device)
+        self._conv("tcn", (KT, 1, f, f), device)
+        self._bn("bn2", f, device)
+        if self.kind == "conv":
+            self._conv("res", (1, 1, in_channels, f), device)
+            self._bn("res_bn", f, device)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        k = state_dict.get(prefix + "sgcn.kernel")
+        if self.kind is None and k is not None:
+            kind = "conv" if prefix + "res_kernel" in state_dict else ("none" if not self.residual else "identity")
+            self.build(k.shape[-2], k.device if k.is_cuda else "cuda", kind)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def _names(self):
+        """(engine name, this module's tensor) of every trainable parameter, in the engine's order"""
+        out = [("l0.gcn.kernel", self.sgcn.kernel), ("l0.gcn.bias", self.sgcn.bias)]
+        for e, m in (("bn1.gamma", "bn1_gamma"), ("bn1.beta", "bn1_beta"), ("tcn.kernel", "tcn_kernel"), ("tcn.bias", "tcn_bias"),
+                     ("bn2.gamma", "bn2_gamma"), ("bn2.beta", "bn2_beta")):
+            out.append(("l0." + e, getattr(self, m)))
+        if self.kind == "conv":
+            for e, m in (("res.kernel", "res_kernel"), ("res.bias", "res_bias"), ("res_bn.gamma", "res_bn_gamma"),
+                         ("res_bn.beta", "res_bn_beta")):
+                out.append(("l0." + e, getattr(self, m)))
+        return out
+
+    def _engine_names(self):
+        return [k for k, _ in self._names()]
+
+    # ---- the one-block engine behind the layer
+    def _engine(self, A, V, device):
+        """the engine for this A: gather tables for a fixed sparse A (rebuilt when A is another tensor or was edited in place; the
+        tensor is kept, so its address cannot be reused by another), the dense path otherwise"""
+        dense = A.requires_grad
+        if not dense:
+            key = (A.data_ptr(), A._version)
+            if self._tables_of is None or self._tables_of[0] is not A or self._tables_of[1] != key:
+                host = A.detach().cpu().numpy().astype(np.float64)
+                try:                     # checked on the host first: a dense A must not leave the engine's tables half replaced
+                    gather_lists(host.astype(np.float32), False), gather_lists(host.astype(np.float32), True)
+                    tables = True
+                except ValueError:       # denser than the gather lists hold
+                    tables = False
+                if tables and False in self._engines:
+                    self._engines[False]._init_adjacency(host)
+                elif tables:
+                    self._engines[False] = self._make_engine(host, V, device, False)
+                self._tables_of = (A, key, tables)
+            dense = not self._tables_of[2]
+        if dense:
+            if V > 32:
+                raise ValueError("the dense adjacency path is built for V <= 32 (got %d)" % V)
+            if True not in self._engines:
+                self._engines[True] = self._make_engine(np.zeros((KS, V, V)), V, device, True)
+            eng = self._engines[True]
+            eng.train_adjacency = bool(A.requires_grad)
+            eng.p["adjacency_matrix"].copy_(A.detach())
+        else:
+            eng = self._engines[False]
+        with torch.no_grad():
+            for k, t in self._names():
+                eng.p[k].copy_(t)
+        for name in ("bn1", "bn2") + (("res_bn",) if self.kind == "conv" else ()):     # the statistics ARE this module's buffers
+            eng.bn["l0." + name].moving_mean = getattr(self, name + "_moving_mean")
+            eng.bn["l0." + name].moving_var = getattr(self, name + "_moving_var")
+        return eng
+
+    def _make_engine(self, A_host, V, device, dense):
+        eng = STGCN(num_classes=4, in_channels=self.cin, num_node=V, A=A_host, device=device,
+                    blocks=[(self.filters, self.stride, self.kind != "none")], mfma="fp32", trainable_adjacency=dense)
+        assert eng.kinds[0] == self.kind
+        return eng
+
+    def forward(self, x, A, training=None):
+        _require(x, 4, "x (B, C, T, V)")
+        _require(A, 3, "A (K, V, V)")
+        B, C, T, V = x.shape
+        if tuple(A.shape) != (KS, V, V) or V > 64:
+            raise ValueError("A must be (%d, V, V) with V = %d <= 64, got %s" % (KS, V, tuple(A.shape)))
+        if training is None:
+            training = self.training
+        self.build(C, x.device)
+        eng = self._engine(A, V, x.device)
+        self._calls += 1
+        if not training:
+            y, To, _ = eng.block_forward(0, to_cn(x), B, T, False)
+            return from_cn(y, (B, self.filters, To, V)), A
+        return _BlockFunction.apply(x, A, self, eng, *[t for _, t in self._names()]), A

@@ -184,6 +184,9 @@ SIGNATURES = {
     "sar_graph_dense_t_bwd_data_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _i, _i, _fp]),
     "sar_graph_dense_t_dadj_slab_floats": (_i64, [_i, _i, _i, _i]),
     "sar_graph_dense_t_dadj_f32": (_i, [_fp, _i64, _fp, _i64, _i, _i, _i, _i, _i, _fp, _fp, _fp]),
+    "sar_graph_sample_fwd_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _fp]),
+    "sar_graph_sample_bwd_data_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _fp]),
+    "sar_graph_sample_dadj_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _i, _i, _i, _fp]),
     # bf16 configuration: CN8 activations
     "sar_conv_gemm_cn8_nparts": (_i, [C.POINTER(ConvDesc)]),
     "sar_conv_gemm_cn8": (_i, [C.POINTER(ConvDesc), _fp, _fp]),

@@ -757,6 +757,28 @@ def graph_dense_t_dA(y, dout, dAt, K, F, V, B, T):
                                          ptr(_f32(dAt)), stream_ptr()), "sar_graph_dense_t_dadj_f32")
 
 
+# ------------------------------------------------------------------------------------------------ adjacency per sample
+def graph_sample_fwd(y, A, out, F, V, N):
+    """out[m, (n,:)] = y[m, (n,:)] . A[n] (sar_graph_sample_fwd_f32); A (N, V, V) contiguous, y / out CN rows of >= N V columns"""
+    assert A.is_contiguous() and tuple(A.shape) == (N, V, V), "A must be a contiguous (N, V, V) table"
+    check(L.load().sar_graph_sample_fwd_f32(ptr(_f32(y)), y.stride(0), ptr(_f32(A)), ptr(_f32(out)), out.stride(0), F, V, N,
+                                            stream_ptr()), "sar_graph_sample_fwd_f32")
+
+
+def graph_sample_bwd_data(dout, A, dy, F, V, N):
+    """dy[m, (n,:)] = dout[m, (n,:)] . A[n]^T (sar_graph_sample_bwd_data_f32)"""
+    assert A.is_contiguous() and tuple(A.shape) == (N, V, V), "A must be a contiguous (N, V, V) table"
+    check(L.load().sar_graph_sample_bwd_data_f32(ptr(_f32(dout)), dout.stride(0), ptr(_f32(A)), ptr(_f32(dy)), dy.stride(0), F, V, N,
+                                                 stream_ptr()), "sar_graph_sample_bwd_data_f32")
+
+
+def graph_sample_dA(y, dout, dA, F, V, N):
+    """dA (N, V, V) contiguous: dA[n] = y[:, (n,:)]^T . dout[:, (n,:)] (sar_graph_sample_dadj_f32)"""
+    assert dA.is_contiguous() and tuple(dA.shape) == (N, V, V), "dA must be a contiguous (N, V, V) table"
+    check(L.load().sar_graph_sample_dadj_f32(ptr(_f32(y)), y.stride(0), ptr(_f32(dout)), dout.stride(0), ptr(_f32(dA)), F, V, N,
+                                             stream_ptr()), "sar_graph_sample_dadj_f32")
+
+
 # ------------------------------------------------------------------------------------------------ graph isomorphism conv
 def conv_gemm_nparts(B, V, T_src, T_out, Kc, M, taps=1, stride=1, pad=0, transposed=False, epi=L.SAR_EPI_STATS):
     """partial sums per output row that sar_conv_gemm_f32 (TEMPORAL) writes for this geometry"""

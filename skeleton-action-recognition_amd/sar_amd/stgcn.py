@@ -570,6 +570,31 @@ class STGCN:
             keep[pre + "g"], keep[pre + "u"], keep[pre + "y"] = g, u, y
         return y, To
 
+    # ------------------------------------------------------------------ one block on its own (models/stgcn.py SpatioTemporalGraphConv)
+    # The layer-level class runs block i of a (one-block) engine on a CN tensor of its own: the block's forward and backward ARE
+    # _block_forward / _block_backward, with what forward() / backward() do around them for that block.
+    def block_forward(self, i, X, B, T, training):
+        """X [cin][B T V] -> (y [f][B To V], To, what block_backward needs or None)"""
+        f, s, _ = self.blocks[i]
+        saved = {"blocks": []}
+        y, To = self._block_forward(i, X, X.shape[0], f, s, B, T, training, saved, None)
+        return y, To, (saved["blocks"][0] if training else None)
+
+    def block_backward(self, i, sb, dY, B):
+        """dY [f][B To V] (overwritten) -> dX [cin][B T V]; the block's gradients (and a trainable adjacency's) are in self.g"""
+        if self._wT_perm is not None:
+            self._wT_perm.run(self.flat, self._wT)
+        if self.dense_A:
+            self._dense_backward_begin(dY.device)
+        dX, _ = self._block_backward(i, sb, dY, B, None, None)
+        if self.dense_A:
+            if self.train_adjacency:
+                self._dense_backward_end()
+            else:
+                self._dA_layers = None
+        self._finish_backward(None)
+        return dX
+
     def _join_aux(self):
         """the main chain waits for what forward() forked onto the third stream (once per step)"""
         if self._aux_pending:
