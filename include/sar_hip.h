@@ -654,6 +654,10 @@ int sar_graph_sample_dadj_f32(const float* y, int64_t ld_y, const float* dout, i
  *                           sum s^2) per workgroup for the BatchNorm that follows (models/stgin.py:28), nparts = sar_gin_nparts(n)
  *   sar_gin_bwd_reduce_f32  dz = ds[c] where a*scale+shift > 0 else 0; partials[K*C][nparts][2] = (sum dz, sum dz*(a - mean))
  *   sar_gin_bwd_apply_f32   da[k*C + c] = k1*dz + k2*a + k3  (k1..k3 from sar_bn_bwd_finalize_f32; da may alias a)
+ *                           Leading dimensions: every ld >= n is taken by sar_gin_bwd_apply_f32 and by sar_gin_sum_fwd_f32 without
+ *                           partials.  The two reducing launches size `partials` by sar_gin_nparts(n), which counts float4 chunks
+ *                           when n % 4 == 0: then the rows must be float4 rows as well (every ld % 4 == 0, 16-byte aligned
+ *                           pointers), SAR_E_ARG otherwise; with n % 4 != 0 every ld >= n is taken
  *   sar_gin_eps_grad_f32    the self slice's first convolution is W . ((1 + eps) x): given G = dout . x^T (weight gradient
  *                           taken on the un-scaled x), deps[0] = <G, W> and G *= (1 + eps[0]) in place
  * ------------------------------------------------------------------------------------------------ */

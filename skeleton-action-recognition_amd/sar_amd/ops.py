@@ -17,7 +17,10 @@ _PROFILE_SHAPES = __import__("os").environ.get("SAR_PROFILE_SHAPES", "0") == "1"
 
 
 def _f32(t):
-    assert t is None or (t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()), "need contiguous cuda float32"
+    # a 2-D operand may be a row-strided view (unit column stride, ld = stride(0) >= the row length): the ABI takes every `ld`
+    assert t is None or (t.dtype == torch.float32 and t.is_cuda and
+                         (t.is_contiguous() or (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]))), \
+        "need cuda float32, contiguous or a 2-D view with unit column stride"
     return t
 
 

@@ -66,3 +66,65 @@ def graph_ref(x, kernel, bias, A, dev_tables):
         if bias is not None:
             out += bias.double()[k * f:(k + 1) * f].view(1, -1, 1, 1) * A[k].double().sum(dim=0).view(1, 1, 1, -1)
     return out
+
+
+# ---- guard bands: an operand as a view into a larger allocation whose every other element holds a known fill (tests/test_gpu_guard_bands.py)
+
+NAN = float("nan")       # padding of inputs: whatever reads it and lets it reach a result shows
+SENTINEL = -7.25         # padding of outputs (tests/test_gpu_graph_sample.py's poison value)
+MASK_FILL = 0xA5         # padding of uint8 mask buffers
+
+
+def _bits(t):
+    """the bit patterns of a tensor (a NaN equals itself)"""
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def guarded(src_or_shape, pad, fill, dev, front=4, back=2, dtype=torch.float32):
+    """(view, whole): `whole` is ONE allocation of (front + C + back, n + pad) elements holding `fill`; view = whole[front:front + C, :n]
+    holds `src` when a (C, n) tensor is given.  front = 4 rows keep the view's base 16-byte aligned for every leading dimension, so
+    an odd `pad` changes only the alignment of the rows behind the first."""
+    src = src_or_shape if torch.is_tensor(src_or_shape) else None
+    C, n = src.shape if src is not None else src_or_shape
+    whole = torch.full((front + C + back, n + pad), fill, dtype=dtype, device=dev)
+    view = whole[front:front + C, :n]
+    if src is not None:
+        view.copy_(src)
+    return view, whole
+
+
+def guarded_flat(src_or_n, fill, dev, k=8, dtype=torch.float32):
+    """(view, whole) of a 1-D range: k elements of `fill` in front of and behind the n live ones (k a multiple of 4: the view stays
+    16-byte aligned)"""
+    assert k % 4 == 0
+    src = src_or_n if torch.is_tensor(src_or_n) else None
+    n = src.numel() if src is not None else int(src_or_n)
+    whole = torch.full((k + n + k,), fill, dtype=dtype, device=dev)
+    view = whole[k:k + n]
+    if src is not None:
+        view.copy_(src.reshape(-1))
+    return view, whole
+
+
+def assert_guards_untouched(whole, view_shape, fill, front=4, back=2, what=""):
+    """every element of `whole` outside whole[front:front + C, :n] still holds `fill`, bit for bit"""
+    C, n = view_shape
+    assert whole.dim() == 2 and whole.shape[0] == front + C + back and whole.shape[1] >= n, "%s: not a guarded allocation" % what
+    want = _bits(torch.full((1,), fill, dtype=whole.dtype, device=whole.device))
+    bad = _bits(whole) != want
+    bad[front:front + C, :n] = False
+    if bool(bad.any()):
+        r, c = [int(v) for v in bad.nonzero()[0]]
+        raise AssertionError("%s: guard element (row %d, column %d) of a (%d, %d) view at row %d, ld %d was overwritten with %r (%d in all)"
+                             % (what, r - front, c, C, n, front, whole.shape[1], whole[r, c].item(), int(bad.sum())))
+
+
+def assert_flat_guards_untouched(whole, n, fill, k=8, what=""):
+    assert whole.dim() == 1 and whole.numel() == n + 2 * k, "%s: not a guarded range" % what
+    want = _bits(torch.full((1,), fill, dtype=whole.dtype, device=whole.device))
+    bad = _bits(whole) != want
+    bad[k:k + n] = False
+    if bool(bad.any()):
+        i = int(bad.nonzero()[0])
+        raise AssertionError("%s: guard element %d of a %d-element range was overwritten with %r (%d in all)"
+                             % (what, i - k, n, whole[i].item(), int(bad.sum())))
