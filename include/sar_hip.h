@@ -636,6 +636,26 @@ int sar_graph_sample_bwd_data_f32(const float* dout, int64_t ld_dout, const floa
 int sar_graph_sample_dadj_f32(const float* y, int64_t ld_y, const float* dout, int64_t ld_dout, float* dA, int F, int V, int N,
                               sar_stream_t s);
 
+/* The graph isomorphism aggregation with a per-sample adjacency (models/gcn.py:89-93 GraphIsoConv.call:
+ * einsum('ncv,nvw->ncw', x, A + diag(1 + epsilon))) on the same kernel and with the same layouts and limits (1 <= V <= 512 else
+ * SAR_E_UNSUP, N*V < 2^31, every ld >= N*V; all checked before any launch).  A + diag(..) is never formed: the self term
+ * (1 + eps[0]) * operand is added in the contraction's epilogue, one fmaf per element.  eps: DEVICE pointer to the layer's scalar
+ * (no host read-back).  With eps[0] = -1 the two equal sar_graph_sample_fwd / bwd_data_f32 bit for bit (up to the sign of a zero).
+ *   fwd       out[m, (n,w)] = sum_v x[m, (n,v)]    * A[n, v, w] + (1 + eps[0]) * x[m, (n,w)]
+ *   bwd_data  dx [m, (n,v)] = sum_w dout[m, (n,w)] * A[n, v, w] + (1 + eps[0]) * dout[m, (n,v)]
+ *   dA        is sar_graph_sample_dadj_f32(x, dout) unchanged: the self term does not depend on A
+ *   eps_grad  deps[0] = sum_{m,n,v} x[m, (n,v)] * dout[m, (n,v)]: both operands streamed once (16 B per lane when both ld % 4 == 0
+ *             and both pointers are 16-byte aligned, element loads otherwise), one fp32 partial per workgroup in `scratch`
+ *             (sar_gin_sample_eps_grad_scratch_floats(F, V, N) floats), then one workgroup adds the partials in a fixed order in
+ *             fp64.  No atomics: repeated launches are bitwise equal. */
+int sar_gin_sample_fwd_f32(const float* x, int64_t ld_x, const float* A, const float* eps, float* out, int64_t ld_out, int F, int V,
+                           int N, sar_stream_t s);
+int sar_gin_sample_bwd_data_f32(const float* dout, int64_t ld_dout, const float* A, const float* eps, float* dx, int64_t ld_dx, int F,
+                                int V, int N, sar_stream_t s);
+int64_t sar_gin_sample_eps_grad_scratch_floats(int F, int V, int N);
+int sar_gin_sample_eps_grad_f32(const float* x, int64_t ld_x, const float* dout, int64_t ld_dout, int F, int V, int N, float* scratch,
+                                float* deps, sar_stream_t s);
+
 /* ------------------------------------------------------------------------------------------------
  * Graph isomorphism convolution, SURVEY.md 8(f)-4 (models/gcn.py:112-163 GraphIsoConvTD as used by models/stgin.py:24-25):
  * fp32 CN layout; the K branch MLPs of a layer are stacked along the channel axis (row k*C + c).
@@ -660,6 +680,11 @@ int sar_graph_sample_dadj_f32(const float* y, int64_t ld_y, const float* dout, i
  *                           pointers), SAR_E_ARG otherwise; with n % 4 != 0 every ld >= n is taken
  *   sar_gin_eps_grad_f32    the self slice's first convolution is W . ((1 + eps) x): given G = dout . x^T (weight gradient
  *                           taken on the un-scaled x), deps[0] = <G, W> and G *= (1 + eps[0]) in place
+ *   sar_gin_eps_grad_bn_f32 the same gradient for a self slice (1 + eps) x that feeds Conv -> BatchNorm in training mode, in closed
+ *                           form from that BatchNorm's backward: deps[0] = bn_eps / (1 + eps[0]) * sum_c gamma[c] dgamma[c] rstd[c]^2
+ *                           (fp64 sum, fixed order).  BatchNorm cancels the scale of its input up to bn_eps, so d epsilon is ~1e-3 of
+ *                           the terms <x, dz> adds up: fp32 leaves it 1e-3 .. 1e-1 of relative error by that route (and by
+ *                           sar_gin_eps_grad_f32), this form the error of dgamma.  With 1 + eps[0] == 0 deps is left as it is
  * ------------------------------------------------------------------------------------------------ */
 int sar_gin_nparts(int64_t n);
 int sar_gin_adjacency_f32(const float* A, int Km1, int V, const float* eps, float* table, float* scale, int C, float* slice_scale,
@@ -672,6 +697,8 @@ int sar_gin_bwd_apply_f32(const float* ds, int64_t ld_ds, const float* a, int64_
                           const float* k1, const float* k2, const float* k3, int K, int C, int64_t n, float* da, int64_t ld_da,
                           sar_stream_t s);
 int sar_gin_eps_grad_f32(float* G, const float* W, int64_t n, const float* eps, float* deps, sar_stream_t s);
+int sar_gin_eps_grad_bn_f32(const float* gamma, const float* dgamma, const float* rstd, int C, float bn_eps, const float* eps,
+                            float* deps, sar_stream_t s);
 int sar_graph_gather_sum_f32(const float* in, int64_t ld_in, const int32_t* idx, const float* wt, const int32_t* nz_host,
                              const float* scale, int K, int F, int V, int64_t n, float* out, int64_t ld_out, const float* add,
                              int64_t ld_add, sar_stream_t s);

@@ -162,6 +162,29 @@ __global__ __launch_bounds__(1024) void gin_eps_grad_kernel(float* G, const floa
   }
 }
 
+// d epsilon of a self slice that feeds Conv -> BatchNorm (training): deps = bn_eps / (1 + eps) sum_c gamma[c] dgamma[c] rstd[c]^2.
+// With z = (1 + eps) x, a = W z + b and da the BatchNorm-backward gradient of a (which sums to zero per channel),
+//   (1 + eps) d eps = <z, W^T da> = <a - b, da> = <a - mean, da> = sum_c gamma rstd S2 (1 - var rstd^2),  S2 = sum dz (a - mean),
+// and dgamma = rstd S2, 1 - var rstd^2 = bn_eps rstd^2.  BatchNorm is invariant to the scale of its input up to bn_eps, so d eps is a
+// difference of large terms that nearly cancel (|d eps| ~ 1e-3 of their scale): <x, dz> or the trace of the table's gradient leave
+// 1e-3 .. 1e-1 of relative error in fp32, this form the error of dgamma.  fp64 sum, fixed order.  1 + eps == 0: deps is left as it is.
+__global__ __launch_bounds__(TPB) void gin_eps_grad_bn_kernel(const float* __restrict__ gamma, const float* __restrict__ dgamma,
+                                                              const float* __restrict__ rstd, int C, float bn_eps,
+                                                              const float* __restrict__ eps, float* deps) {
+  const float e = 1.f + eps[0];
+  if (e == 0.f) return;      // uniform
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < C; i += TPB) {
+    const double r = rstd[i];
+    acc += (double)gamma[i] * (double)dgamma[i] * r * r;
+  }
+  __shared__ double red[4];
+  acc = wave_sum_d(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) deps[0] = (float)(((red[0] + red[1]) + (red[2] + red[3])) * (double)bn_eps / (double)e);
+}
+
 // Frame-local weighted gathers for a FIXED sparse adjacency (<= 4 entries per joint: sar_amd/graph_tables.py), the form the
 // ST-GCN kernels fold into their operand loads, as stand-alone HBM-bound passes for the graph isomorphism convolution:
 //   MODE 0 (sum):    out[m, (t,w)] = sum_k scale[k] sum_j wt[k][w][j] in[k F + m, (t, idx[k][w][j])]  (+ add[m, (t,w)])
@@ -274,6 +297,14 @@ extern "C" int sar_gin_eps_grad_f32(float* G, const float* W, int64_t n, const f
   SAR_REQUIRE(G && W && n > 0 && eps && deps, "sar_gin_eps_grad: bad arguments");
   hipLaunchKernelGGL(gin_eps_grad_kernel, dim3(1), dim3(1024), 0, as_stream(st_), G, W, n, eps, deps);
   SAR_LAUNCH_CHECK("sar_gin_eps_grad_f32");
+  return 0;
+}
+
+extern "C" int sar_gin_eps_grad_bn_f32(const float* gamma, const float* dgamma, const float* rstd, int C, float bn_eps, const float* eps,
+                                       float* deps, sar_stream_t st_) {
+  SAR_REQUIRE(gamma && dgamma && rstd && C > 0 && bn_eps > 0.f && eps && deps, "sar_gin_eps_grad_bn: bad arguments");
+  hipLaunchKernelGGL(gin_eps_grad_bn_kernel, dim3(1), dim3(TPB), 0, as_stream(st_), gamma, dgamma, rstd, C, bn_eps, eps, deps);
+  SAR_LAUNCH_CHECK("sar_gin_eps_grad_bn_f32");
   return 0;
 }
 

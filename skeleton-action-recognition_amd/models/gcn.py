@@ -22,7 +22,14 @@ The layers convert NCHW <-> the kernels' CN layout ([C][B*T*V]) at their boundar
 of these layers pays that conversion PER LAYER; the whole-network engines (models/stgcn.py, stgin.py, stpgcn.py, stgcn_debug.py)
 convert once.  This is the interface for variants that are not pre-built, not the fast path.
 
-Not here: GraphIsoConv / GraphIsoConvTD (models/gcn.py:54-163) -- models/stgin.py covers that model as a whole.
+The graph isomorphism layers (models/gcn.py:54-163; `filters` is the list of MLP widths, activation 'relu' only):
+
+  GraphIsoConv(filters, return_logits=False)        forward(x (N,C,V),   A (N,V,V),   training) -> (x (N,filters[-1],V),   A)    models/gcn.py:54-93
+  GraphIsoConvTD(filters, kernel_size=3)            forward(x (B,C,T,V), A (K-1,V,V), training) -> (x (B,filters[-1],T,V), A)    models/gcn.py:112-163
+
+Both own the trainable scalar `epsilon` and the MLP(s) `mlp.{i}.*` / `mlps.{k}.{i}.*` (kernel, bias, gamma, beta; moving_mean and
+moving_var as buffers; BatchNorm eps 1e-3, momentum 0.99); see the classes.  training=False uses the moving statistics and is
+forward only.
 """
 import math
 
@@ -34,6 +41,8 @@ from sar_amd import ops
 
 GRAPH_CONV_EINSUM = "ncv,nvw->ncw"
 GRAPH_CONV_TD_EINSUM = "nkctv,kvw->nctw"
+GRAPH_ISO_CONV_TD_EINSUM = "nctv,kvw->nkctw"
+BN_EPS, BN_MOMENTUM = 1e-3, 0.99          # Keras BatchNormalization defaults, as sar_amd/stgcn.py
 
 
 def _require(x, ndim, what):
@@ -326,3 +335,428 @@ class AdjGraphConv(_Conv1x1Layer):
             raise ValueError("x has %d joints, adjacency_matrix %d" % (x.shape[3], self.adjacency_matrix.shape[1]))
         self.build(x.shape[1], x.device)
         return _GraphConvTDDenseFn.apply(x, self.adjacency_matrix, self.kernel, self.bias)
+
+
+# ================================================================================================ graph isomorphism layers
+class _BNState:
+    """what one BatchNorm of one call leaves for its consumers and for backward (fresh per call: nothing is shared between calls)"""
+
+    def __init__(self, C, device):
+        z = lambda: torch.empty(C, dtype=torch.float32, device=device)
+        self.mean, self.rstd, self.scale, self.shift = z(), z(), z(), z()
+        self.k1, self.k2, self.k3 = z(), z(), z()
+
+
+def _rows(t, k, h):
+    return t[k * h:(k + 1) * h]
+
+
+class _GinMLPLayer(torch.nn.Module):
+    """one Conv(f, 1x1) [-> BatchNormalization(axis=1) -> ReLU] of a GIN MLP: `kernel` / `bias` in the Keras layout, `gamma` / `beta`
+    and the buffers `moving_mean` / `moving_var` where the layer has a BatchNorm; created by build()"""
+
+    def __init__(self, out_channels, kernel_rank, has_bn):
+        super().__init__()
+        self.out_channels, self._kernel_rank, self.has_bn = int(out_channels), kernel_rank, bool(has_bn)
+        self.register_parameter("kernel", None)
+        self.register_parameter("bias", None)
+        if self.has_bn:
+            self.register_parameter("gamma", None)
+            self.register_parameter("beta", None)
+            self.register_buffer("moving_mean", None)
+            self.register_buffer("moving_var", None)
+
+    def build(self, in_channels, device):
+        f = self.out_channels
+        new = lambda fill: torch.full((f,), fill, dtype=torch.float32, device=device)
+        self.kernel = torch.nn.Parameter(torch.empty((1,) * (self._kernel_rank - 2) + (int(in_channels), f), dtype=torch.float32,
+                                                     device=device))
+        variance_scaling_(self.kernel)
+        self.bias = torch.nn.Parameter(new(0.0))
+        if self.has_bn:
+            self.gamma, self.beta = torch.nn.Parameter(new(1.0)), torch.nn.Parameter(new(0.0))
+            self.moving_mean, self.moving_var = new(0.0), new(1.0)
+
+    def tensors(self):
+        return [self.kernel, self.bias] + ([self.gamma, self.beta] if self.has_bn else [])
+
+
+def _check_gin_arguments(filters, activation, return_logits, einsum, default_einsum):
+    if activation != "relu":
+        raise ValueError("activation %r is not implemented (only 'relu' is)" % (activation,))
+    _require_einsum(einsum, default_einsum)
+    if not isinstance(filters, list) or not filters or not all(isinstance(f, int) and f > 0 for f in filters):
+        raise ValueError("filters must be a non-empty list of positive ints, got %r" % (filters,))
+
+
+def _mlp(filters, kernel_rank, return_logits):
+    last = len(filters) - 1
+    return torch.nn.ModuleList(_GinMLPLayer(f, kernel_rank, i < last or not return_logits) for i, f in enumerate(filters))
+
+
+def _bn_forward(st, rows, result, count, layer, training, unbiased):
+    """BatchNorm of `layer` into rows `rows` of the (possibly stacked) state `st`: training, from the producer's statistics
+    (moving statistics updated); inference, from the moving statistics"""
+    view = lambda t: t if rows is None else _rows(t, rows, layer.out_channels)
+    if training:
+        ops.bn_finalize(result[0], result[1], layer.out_channels, count, BN_EPS, BN_MOMENTUM, unbiased, layer.gamma, layer.beta,
+                        layer.moving_mean, layer.moving_var, view(st.mean), view(st.rstd), view(st.scale), view(st.shift))
+    else:
+        ops.bn_eval_affine(layer.gamma, layer.beta, layer.moving_mean, layer.moving_var, BN_EPS, view(st.scale), view(st.shift))
+
+
+def _bn_backward(st, rows, sums, count, layer):
+    """(dgamma, dbeta) of `layer`'s BatchNorm and k1..k3 of its backward apply pass, from (partials (f, nparts, 2), nparts) =
+    (sum dz, sum dz (a - mean)) per channel and partial"""
+    f = layer.out_channels
+    view = lambda t: t if rows is None else _rows(t, rows, f)
+    dg = torch.empty(2 * f, dtype=torch.float32, device=sums[0].device)
+    ops.bn_bwd_finalize(sums[0], sums[1], sums[1] * 2, 2, 0, 1, f, count, layer.gamma, view(st.mean), view(st.rstd), dg[:f], dg[f:],
+                        view(st.k1), view(st.k2), view(st.k3))
+    return dg[:f], dg[f:]
+
+
+def _unpack(layers, params):
+    """the flat parameter list of Function.apply -> per layer (kernel, bias, gamma, beta) holders that read like the modules"""
+    out, i = [], 0
+    for l in layers:
+        n = 4 if l.has_bn else 2
+        out.append(params[i:i + n])
+        i += n
+    return out
+
+
+class _GraphIsoConvFn(torch.autograd.Function):
+    """GraphIsoConv as one node: the fused aggregation (csrc/graph_sample.hip, SELF), the MLP as 1x1 conv-GEMMs with the statistics
+    epilogue and each hidden BN + ReLU folded into the next product's operand load, the last BN + ReLU as sar_gin_sum_fwd_f32 (K = 1).
+    Everything backward needs is kept in ctx."""
+
+    @staticmethod
+    def forward(ctx, x, A, layer, training, eps, *params):
+        N, C, V = x.shape
+        n, dev = N * V, x.device
+        mlp = list(layer.mlp)
+        geo = dict(taps=1, stride=1, pad=0, split=None, **_column_geometry(N, V))
+        new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
+        X = to_cn(x)
+        agg = new(C)
+        ops.gin_sample_fwd(X, A, eps, agg, C, V, N)
+        acts, states, src, pro, cin = [], [], agg, None, C
+        for l in mlp:
+            f = l.out_channels
+            a = new(f)
+            res = ops.conv_gemm(L.SAR_CONV_TEMPORAL, src, a, l.kernel.view(cin, f), 0, f, Kc=cin, M=f, bias=l.bias, pro=pro,
+                                pro_relu=pro is not None, epi=L.SAR_EPI_STATS if (l.has_bn and training) else L.SAR_EPI_NONE, **geo)
+            st = None
+            if l.has_bn:
+                st = _BNState(f, dev)
+                _bn_forward(st, None, res, n, l, training, False)      # Keras' non-fused 3-D path: biased moving variance
+                pro = (st.scale, st.shift)
+            acts.append(a), states.append(st)
+            src, cin = a, f
+        out = src
+        if mlp[-1].has_bn:
+            out = new(cin)
+            ops.gin_sum_fwd(src, pro[0], pro[1], 1, out)
+        ctx.save_for_backward(A, eps, *params)
+        ctx.layers, ctx.training, ctx.geo, ctx.shape = mlp, training, geo, (N, C, V)
+        ctx.X, ctx.agg, ctx.acts, ctx.states = X, agg, acts, states
+        return from_cn(out, (N, cin, V))
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.training:
+            raise RuntimeError("backward through GraphIsoConv(x, A, training=False) is not supported (inference path)")
+        A, eps = ctx.saved_tensors[:2]
+        P = _unpack(ctx.layers, ctx.saved_tensors[2:])
+        mlp, geo, (N, C, V), acts, states = ctx.layers, ctx.geo, ctx.shape, ctx.acts, ctx.states
+        n, dev = N * V, dout.device
+        new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
+        grads = [None] * len(ctx.saved_tensors[2:])
+        base = [sum(4 if l.has_bn else 2 for l in mlp[:i]) for i in range(len(mlp))]
+        da = to_cn(dout.contiguous())
+        last = len(mlp) - 1
+        if mlp[last].has_bn:                  # the last BN + ReLU
+            st, a = states[last], acts[last]
+            sums = ops.gin_bwd_reduce(da, a, st.scale, st.shift, st.mean, 1)
+            grads[base[last] + 2], grads[base[last] + 3] = _bn_backward(st, None, sums, n, _Holder(mlp[last], P[last]))
+            dz = new(a.shape[0])
+            ops.gin_bwd_apply(da, a, st.scale, st.shift, (st.k1, st.k2, st.k3), 1, dz)
+            da = dz
+        for i in range(last, -1, -1):
+            l, f = mlp[i], mlp[i].out_channels
+            src = acts[i - 1] if i else ctx.agg
+            cin = src.shape[0]
+            pst = states[i - 1] if i else None
+            pro = (pst.scale, pst.shift) if i else None
+            W = P[i][0].view(cin, f)
+            flat = torch.empty(cin * f + f, dtype=torch.float32, device=dev)
+            ops.conv_wgrad(L.SAR_CONV_TEMPORAL, src, da, flat, Kc=cin, M=f, pro=pro, pro_relu=pro is not None, w_stride_tap=0,
+                           w_stride_c=f, wsize=cin * f, bsize=f, **geo)
+            grads[base[i]], grads[base[i] + 1] = flat[:cin * f].view(P[i][0].shape), flat[cin * f:]
+            WT = torch.empty((f, cin), dtype=torch.float32, device=dev)
+            ops.transpose(W, WT, 1, cin, f)
+            dsrc = new(cin)
+            if i:                             # through the hidden BN + ReLU: masked data gradient + BatchNorm-backward sums
+                sums = ops.conv_gemm(L.SAR_CONV_TEMPORAL, da, dsrc, WT, 0, cin, Kc=f, M=cin, transposed=True, epi=L.SAR_EPI_MASK,
+                                     aux=src, aux_affine=pro, aux_mean=pst.mean, **geo)
+                grads[base[i - 1] + 2], grads[base[i - 1] + 3] = _bn_backward(pst, None, sums, n, _Holder(mlp[i - 1], P[i - 1]))
+                ops.affine2(dsrc, src, (pst.k1, pst.k2, pst.k3), dsrc)
+            else:
+                ops.conv_gemm(L.SAR_CONV_TEMPORAL, da, dsrc, WT, 0, cin, Kc=f, M=cin, transposed=True, **geo)
+            da = dsrc
+        need_x, need_A, _, _, need_eps = ctx.needs_input_grad[:5]
+        dx = dA = deps = None
+        if need_eps:
+            deps = torch.empty((), dtype=torch.float32, device=dev)
+            ops.gin_sample_eps_grad(ctx.X, da, deps, C, V, N)
+        if need_A:
+            dA = torch.empty_like(A)
+            ops.graph_sample_dA(ctx.X, da, dA, C, V, N)
+        if need_x:
+            dX = new(C)
+            ops.gin_sample_bwd_data(da, A, eps, dX, C, V, N)
+            dx = from_cn(dX, (N, C, V))
+        return (dx, dA, None, None, deps) + tuple(grads)
+
+
+class _Holder:
+    """a layer's shape with the parameter tensors autograd saved for this call"""
+
+    def __init__(self, layer, params):
+        self.out_channels = layer.out_channels
+        self.gamma = params[2] if layer.has_bn else None
+
+
+class _GinBase(torch.nn.Module):
+    def _all_layers(self):
+        raise NotImplementedError
+
+    def _first_kernel_key(self):
+        raise NotImplementedError
+
+    def build(self, in_channels, device):
+        layers = self._all_layers()
+        if self.epsilon is None:
+            self.epsilon = torch.nn.Parameter(torch.zeros((), dtype=torch.float32, device=device))
+            for chain in layers:
+                cin = int(in_channels)
+                for l in chain:
+                    l.build(cin, device)
+                    cin = l.out_channels
+        elif layers[0][0].kernel.shape[-2] != in_channels:
+            raise ValueError("the layer was built for %d input channels, got %d" % (layers[0][0].kernel.shape[-2], in_channels))
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        k = state_dict.get(prefix + self._first_kernel_key())
+        if self.epsilon is None and k is not None:
+            self.build(k.shape[-2], k.device if k.is_cuda else "cuda")
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+
+class GraphIsoConv(_GinBase):
+    """models/gcn.py:54-93: x = einsum('ncv,nvw->ncw', x, A + diag(1 + epsilon)); x = mlp(x), the MLP a chain of
+    Conv1D(f, 1) -> BatchNormalization(axis=1) -> ReLU over `filters` (return_logits=True: the last layer is the bare Conv1D).
+    Parameters: `epsilon` (), `mlp.{i}.kernel` (1, Cin, f), `mlp.{i}.bias`, `mlp.{i}.gamma` / `.beta` and the buffers
+    `mlp.{i}.moving_mean` / `.moving_var` where layer i has a BatchNorm.  The statistics run over (N, V); the moving variance takes
+    the BIASED batch variance (Keras' non-fused path for 3-D inputs; SURVEY 8(c), the data_bn convention).
+    A + diag(..) is never formed (csrc/graph_sample.hip).  V <= 512, N V < 2^22.  A that requires a gradient gets dA."""
+
+    def __init__(self, filters, activation="relu", return_logits=False, einsum=GRAPH_CONV_EINSUM):
+        super().__init__()
+        _check_gin_arguments(filters, activation, return_logits, einsum, GRAPH_CONV_EINSUM)
+        self.filters, self.return_logits, self.einsum = list(filters), bool(return_logits), einsum
+        self.mlp = _mlp(self.filters, 3, self.return_logits)
+        self.register_parameter("epsilon", None)
+
+    def _all_layers(self):
+        return [list(self.mlp)]
+
+    def _first_kernel_key(self):
+        return "mlp.0.kernel"
+
+    def forward(self, x, A, training=None):
+        _require(x, 3, "x (N, C, V)")
+        _require(A, 3, "A (N, V, V)")
+        N, C, V = x.shape
+        if tuple(A.shape) != (N, V, V) or V > 512:
+            raise ValueError("A must be (N, V, V) = (%d, %d, %d) with V <= 512, got %s" % (N, V, V, tuple(A.shape)))
+        if N * V >= 1 << 22:
+            raise ValueError("N * V = %d columns: the 1x1 products are built for fewer than 2^22" % (N * V))
+        if training is None:
+            training = self.training
+        self.build(C, x.device)
+        params = [t for l in self.mlp for t in l.tensors()]
+        return _GraphIsoConvFn.apply(x, A, self, bool(training), self.epsilon, *params), A
+
+
+class _GraphIsoConvTDFn(torch.autograd.Function):
+    """GraphIsoConvTD as one node, composed from the kernels sar_amd/stgin.py runs for a dense adjacency: the table
+    [A_k^T.., (1 + eps) I] (sar_gin_adjacency_f32), x expanded to the K slices (sar_graph_dense_bwd_data_f32), the K MLPs stacked along
+    the channel axis ([K f][B T V] activations, K f-channel BatchNorm state per MLP layer: the element-wise passes are one launch for
+    all branches; the finalisations run per branch on each MLP's own gamma / beta / moving statistics), the last BN + ReLU + sum over
+    the branches (sar_gin_sum_fwd_f32).  Backward: the table's gradient (sar_graph_dense_dadj_f32 on (dz, x)) gives dA as its transpose
+    and d epsilon as the trace of its self slice, which sar_gin_eps_grad_bn_f32 then replaces by the well-conditioned closed form.
+    Everything backward needs is kept in ctx."""
+
+    @staticmethod
+    def forward(ctx, x, A, layer, training, eps, *params):
+        B, C, T, V = x.shape
+        K, n, dev = layer.kernel_size, B * T * V, x.device
+        mlps = [list(m) for m in layer.mlps]
+        depth = len(mlps[0])
+        geo = dict(B=B, V=V, T_src=T, T_out=T, taps=1, stride=1, pad=0)
+        new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
+        X = to_cn(x)
+        table = torch.empty((K, V, V), dtype=torch.float32, device=dev)
+        escale = torch.empty(C, dtype=torch.float32, device=dev)
+        ops.gin_adjacency(A, eps, table, escale)
+        z = new(K * C)                                          # z[k C + c] = x[c] . A_k, the self slice (1 + eps) x[c]
+        ops.graph_dense_bwd_data(X, table, z, K, C, V, B * T)
+        acts, states, src, cin, prev = [], [], z, C, None
+        for i in range(depth):
+            f = mlps[0][i].out_channels
+            a, st = new(K * f), _BNState(K * f, dev)
+            part = nparts = None
+            if training:
+                nparts = ops.conv_gemm_nparts(Kc=cin, M=f, **geo)
+                part = torch.empty((K * f, nparts, 2), dtype=torch.float32, device=dev)
+            for k in range(K):
+                l = mlps[k][i]
+                ops.conv_gemm(L.SAR_CONV_TEMPORAL, _rows(src, k, cin), _rows(a, k, f), l.kernel.view(cin, f), 0, f, Kc=cin, M=f,
+                              bias=l.bias, pro=(_rows(prev.scale, k, cin), _rows(prev.shift, k, cin)) if prev else None,
+                              pro_relu=prev is not None, epi=L.SAR_EPI_STATS if training else L.SAR_EPI_NONE,
+                              partials_out=_rows(part, k, f) if training else None, split=None, **geo)
+                _bn_forward(st, k, (_rows(part, k, f), nparts) if training else None, n, l, training, True)
+            acts.append(a), states.append(st)
+            src, cin, prev = a, f, st
+        out = new(cin)
+        ops.gin_sum_fwd(src, prev.scale, prev.shift, K, out)
+        ctx.save_for_backward(A, eps, *params)
+        ctx.mlps, ctx.training, ctx.geo, ctx.shape, ctx.K = mlps, training, geo, (B, C, T, V), K
+        ctx.X, ctx.z, ctx.table, ctx.acts, ctx.states = X, z, table, acts, states
+        return from_cn(out, (B, cin, T, V))
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.training:
+            raise RuntimeError("backward through GraphIsoConvTD(x, A, training=False) is not supported (inference path)")
+        A, eps = ctx.saved_tensors[:2]
+        mlps, geo, (B, C, T, V), K, acts, states = ctx.mlps, ctx.geo, ctx.shape, ctx.K, ctx.acts, ctx.states
+        depth = len(mlps[0])
+        flat_layers = [l for m in mlps for l in m]              # the order of `params`: branch by branch
+        P = _unpack(flat_layers, ctx.saved_tensors[2:])
+        at = lambda k, i: k * depth + i
+        grads = [None] * (4 * len(flat_layers))
+        n, dev = B * T * V, dout.device
+        new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
+        ds = to_cn(dout.contiguous())
+        st, a = states[-1], acts[-1]
+        f = mlps[0][-1].out_channels
+        sums = ops.gin_bwd_reduce(ds, a, st.scale, st.shift, st.mean, K)
+        for k in range(K):
+            j = at(k, depth - 1)
+            grads[4 * j + 2], grads[4 * j + 3] = _bn_backward(st, k, (_rows(sums[0], k, f), sums[1]), n, _Holder(mlps[k][-1], P[j]))
+        da = new(K * f)
+        ops.gin_bwd_apply(ds, a, st.scale, st.shift, (st.k1, st.k2, st.k3), K, da)
+        for i in range(depth - 1, -1, -1):
+            f = mlps[0][i].out_channels
+            src = acts[i - 1] if i else ctx.z
+            cin = src.shape[0] // K
+            pst = states[i - 1] if i else None
+            dsrc = new(K * cin)
+            pm = npm = None
+            if i:
+                npm = ops.conv_gemm_nparts(Kc=f, M=cin, transposed=True, epi=L.SAR_EPI_MASK, **geo)
+                pm = torch.empty((K * cin, npm, 2), dtype=torch.float32, device=dev)
+            for k in range(K):
+                j = at(k, i)
+                pro = (_rows(pst.scale, k, cin), _rows(pst.shift, k, cin)) if i else None
+                W = P[j][0].view(cin, f)
+                flat = torch.empty(cin * f + f, dtype=torch.float32, device=dev)
+                ops.conv_wgrad(L.SAR_CONV_TEMPORAL, _rows(src, k, cin), _rows(da, k, f), flat, Kc=cin, M=f, pro=pro,
+                               pro_relu=pro is not None, w_stride_tap=0, w_stride_c=f, wsize=cin * f, bsize=f, split=None, **geo)
+                grads[4 * j], grads[4 * j + 1] = flat[:cin * f].view(P[j][0].shape), flat[cin * f:]
+                WT = torch.empty((f, cin), dtype=torch.float32, device=dev)
+                ops.transpose(W, WT, 1, cin, f)
+                if i:
+                    ops.conv_gemm(L.SAR_CONV_TEMPORAL, _rows(da, k, f), _rows(dsrc, k, cin), WT, 0, cin, Kc=f, M=cin, transposed=True,
+                                  epi=L.SAR_EPI_MASK, aux=_rows(src, k, cin), aux_affine=pro, aux_mean=_rows(pst.mean, k, cin),
+                                  partials_out=_rows(pm, k, cin), split=None, **geo)
+                    jp = at(k, i - 1)
+                    grads[4 * jp + 2], grads[4 * jp + 3] = _bn_backward(pst, k, (_rows(pm, k, cin), npm), n,
+                                                                        _Holder(mlps[k][i - 1], P[jp]))
+                else:
+                    ops.conv_gemm(L.SAR_CONV_TEMPORAL, _rows(da, k, f), _rows(dsrc, k, cin), WT, 0, cin, Kc=f, M=cin, transposed=True,
+                                  split=None, **geo)
+            if i:
+                ops.affine2(dsrc, src, (pst.k1, pst.k2, pst.k3), dsrc)
+            da = dsrc
+        need_x, need_A, _, _, need_eps = ctx.needs_input_grad[:5]
+        dx = dA = deps = None
+        if need_A or need_eps:                 # the table's gradient: dA[k] is its transpose, d epsilon the trace of its self slice
+            dtable = torch.empty((K, V, V), dtype=torch.float32, device=dev)
+            ops.graph_dense_dA(da, ctx.X, dtable, K, C, V, B * T)
+            if need_A:
+                dA = torch.empty_like(A)
+                if K > 1:
+                    ops.transpose(dtable, dA, K - 1, V, V)
+            if need_eps:                       # trace = <dtable[K - 1], I> (sar_gin_eps_grad_f32 also rescales its first operand:
+                deps = torch.empty((), dtype=torch.float32, device=dev)      # dtable is not read again)
+                eye = torch.eye(V, dtype=torch.float32, device=dev)
+                ops.gin_eps_grad(dtable[K - 1], eye, eps, deps)
+                # ... which fp32 leaves 1e-3 .. 1e-1 off: the self slice feeds Conv -> BatchNorm, whose output does not depend on the
+                # scale 1 + eps of its input but for BN_EPS, so d epsilon is what is left of terms that cancel to ~1e-3.  The closed
+                # form from that BatchNorm's backward (csrc/gin.hip) replaces the trace unless 1 + eps == 0
+                j0 = at(K - 1, 0)
+                ops.gin_eps_grad_bn(P[j0][2], grads[4 * j0 + 2], _rows(states[0].rstd, K - 1, mlps[K - 1][0].out_channels), BN_EPS, eps,
+                                    deps)
+        if need_x:
+            dX = new(C)
+            ops.graph_dense_fwd(da, ctx.table, dX, K, C, V, B * T)
+            dx = from_cn(dX, (B, C, T, V))
+        return (dx, dA, None, None, deps) + tuple(grads)
+
+
+class GraphIsoConvTD(_GinBase):
+    """models/gcn.py:112-163: x' = einsum('nctv,kvw->nkctw', x, concat(A, diag(1 + epsilon))); slice k through its own MLP
+    (Conv2D(f, 1x1) -> BatchNormalization(axis=1) -> ReLU over `filters`); sum over the slices.  A is (kernel_size - 1, V, V).
+    Parameters: `epsilon` (), `mlps.{k}.{i}.kernel` (1, 1, Cin, f), `.bias`, `.gamma`, `.beta` and the buffers `.moving_mean` /
+    `.moving_var` (statistics over (B, T, V); unbiased moving variance, the fused 4-D convention of the engines).
+    V <= 32, kernel_size <= 8, B T V < 2^22.  A that requires a gradient gets dA.
+    Not built: return_logits=True (there is no branch sum without the ReLU) raises ValueError; there is no gather-list fast path for a
+    fixed sparse A here -- every A takes the dense contraction (csrc/graph_dense.hip); models/stgin.py stays the fast path for the
+    fixed graph."""
+
+    def __init__(self, filters, kernel_size=3, activation="relu", return_logits=False, einsum=GRAPH_ISO_CONV_TD_EINSUM):
+        super().__init__()
+        _check_gin_arguments(filters, activation, return_logits, einsum, GRAPH_ISO_CONV_TD_EINSUM)
+        if return_logits:
+            raise ValueError("return_logits=True is not built for GraphIsoConvTD (no branch sum without the ReLU)")
+        if not isinstance(kernel_size, int) or not 1 <= kernel_size <= 8:
+            raise ValueError("kernel_size must be an int in 1..8, got %r" % (kernel_size,))
+        self.filters, self.kernel_size, self.return_logits, self.einsum = list(filters), kernel_size, False, einsum
+        self.mlps = torch.nn.ModuleList(_mlp(self.filters, 4, False) for _ in range(kernel_size))
+        self.register_parameter("epsilon", None)
+
+    def _all_layers(self):
+        return [list(m) for m in self.mlps]
+
+    def _first_kernel_key(self):
+        return "mlps.0.0.kernel"
+
+    def forward(self, x, A, training=None):
+        _require(x, 4, "x (B, C, T, V)")
+        _require(A, 3, "A (kernel_size - 1, V, V)")
+        B, C, T, V = x.shape
+        K = self.kernel_size
+        if tuple(A.shape) != (K - 1, V, V):
+            raise ValueError("A must be (kernel_size - 1, V, V) = (%d, %d, %d), got %s" % (K - 1, V, V, tuple(A.shape)))
+        _dense_limits(K, V)
+        if B * T * V >= 1 << 22:
+            raise ValueError("B * T * V = %d columns: the convolutions are built for fewer than 2^22" % (B * T * V))
+        if training is None:
+            training = self.training
+        self.build(C, x.device)
+        params = [t for m in self.mlps for l in m for t in l.tensors()]
+        return _GraphIsoConvTDFn.apply(x, A, self, bool(training), self.epsilon, *params), A

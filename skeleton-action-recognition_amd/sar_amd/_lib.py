@@ -165,6 +165,7 @@ SIGNATURES = {
     "sar_gin_bwd_reduce_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _fp, _fp, _i, _i, _i64, _fp, _fp]),
     "sar_gin_bwd_apply_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, _i, _i, _i64, _fp, _i64, _fp]),
     "sar_gin_eps_grad_f32": (_i, [_fp, _fp, _i64, _fp, _fp, _fp]),
+    "sar_gin_eps_grad_bn_f32": (_i, [_fp, _fp, _fp, _i, _f, _fp, _fp, _fp]),
     # ST-PGCN projection graph convolution (csrc/pgc.hip)
     "sar_pgc_nparts": (_i, [_i64]),
     "sar_pgc_assign_f32": (_i, [_fp, _i64, _i, _i64, _fp, _fp, _fp, _fp, _fp]),
@@ -187,6 +188,10 @@ SIGNATURES = {
     "sar_graph_sample_fwd_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _fp]),
     "sar_graph_sample_bwd_data_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _fp]),
     "sar_graph_sample_dadj_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _i, _i, _i, _fp]),
+    "sar_gin_sample_fwd_f32": (_i, [_fp, _i64, _fp, _fp, _fp, _i64, _i, _i, _i, _fp]),
+    "sar_gin_sample_bwd_data_f32": (_i, [_fp, _i64, _fp, _fp, _fp, _i64, _i, _i, _i, _fp]),
+    "sar_gin_sample_eps_grad_scratch_floats": (_i64, [_i, _i, _i]),
+    "sar_gin_sample_eps_grad_f32": (_i, [_fp, _i64, _fp, _i64, _i, _i, _i, _fp, _fp, _fp]),
     # bf16 configuration: CN8 activations
     "sar_conv_gemm_cn8_nparts": (_i, [C.POINTER(ConvDesc)]),
     "sar_conv_gemm_cn8": (_i, [C.POINTER(ConvDesc), _fp, _fp]),

@@ -782,6 +782,32 @@ def graph_sample_dA(y, dout, dA, F, V, N):
                                              stream_ptr()), "sar_graph_sample_dadj_f32")
 
 
+def gin_sample_fwd(x, A, eps, out, F, V, N):
+    """out[m, (n,:)] = x[m, (n,:)] . A[n] + (1 + eps) x[m, (n,:)] (sar_gin_sample_fwd_f32); eps: the layer's scalar ON THE DEVICE"""
+    assert A.is_contiguous() and tuple(A.shape) == (N, V, V), "A must be a contiguous (N, V, V) table"
+    assert eps.is_cuda and eps.dtype == torch.float32 and eps.numel() == 1, "eps must be one float32 on the device"
+    check(L.load().sar_gin_sample_fwd_f32(ptr(_f32(x)), x.stride(0), ptr(_f32(A)), ptr(eps), ptr(_f32(out)), out.stride(0), F, V, N,
+                                          stream_ptr()), "sar_gin_sample_fwd_f32")
+
+
+def gin_sample_bwd_data(dout, A, eps, dx, F, V, N):
+    """dx[m, (n,:)] = dout[m, (n,:)] . A[n]^T + (1 + eps) dout[m, (n,:)] (sar_gin_sample_bwd_data_f32)"""
+    assert A.is_contiguous() and tuple(A.shape) == (N, V, V), "A must be a contiguous (N, V, V) table"
+    assert eps.is_cuda and eps.dtype == torch.float32 and eps.numel() == 1, "eps must be one float32 on the device"
+    check(L.load().sar_gin_sample_bwd_data_f32(ptr(_f32(dout)), dout.stride(0), ptr(_f32(A)), ptr(eps), ptr(_f32(dx)), dx.stride(0),
+                                               F, V, N, stream_ptr()), "sar_gin_sample_bwd_data_f32")
+
+
+def gin_sample_eps_grad(x, dout, deps, F, V, N, scratch=None):
+    """deps[0] = <x, dout> over the F x N V live elements (sar_gin_sample_eps_grad_f32); deps: one float32 on the device"""
+    lib = L.load()
+    assert deps.is_cuda and deps.dtype == torch.float32 and deps.numel() == 1, "deps must be one float32 on the device"
+    if scratch is None:
+        scratch = torch.empty(lib.sar_gin_sample_eps_grad_scratch_floats(F, V, N), dtype=torch.float32, device=x.device)
+    check(lib.sar_gin_sample_eps_grad_f32(ptr(_f32(x)), x.stride(0), ptr(_f32(dout)), dout.stride(0), F, V, N, ptr(scratch), ptr(deps),
+                                          stream_ptr()), "sar_gin_sample_eps_grad_f32")
+
+
 # ------------------------------------------------------------------------------------------------ graph isomorphism conv
 def conv_gemm_nparts(B, V, T_src, T_out, Kc, M, taps=1, stride=1, pad=0, transposed=False, epi=L.SAR_EPI_STATS):
     """partial sums per output row that sar_conv_gemm_f32 (TEMPORAL) writes for this geometry"""
@@ -851,6 +877,13 @@ def gin_bwd_apply(ds, a, scale, shift, k, K, da):
 def gin_eps_grad(G, W, eps, deps):
     assert G.is_contiguous() and W.is_contiguous() and G.numel() == W.numel()
     check(L.load().sar_gin_eps_grad_f32(ptr(G), ptr(W), G.numel(), ptr(eps), ptr(deps), stream_ptr()), "sar_gin_eps_grad_f32")
+
+
+def gin_eps_grad_bn(gamma, dgamma, rstd, bn_eps, eps, deps):
+    """deps = bn_eps / (1 + eps) sum_c gamma dgamma rstd^2: d epsilon of a self slice in front of Conv -> BatchNorm, from that
+    BatchNorm's backward (sar_gin_eps_grad_bn_f32); deps is left as it is when 1 + eps == 0"""
+    check(L.load().sar_gin_eps_grad_bn_f32(ptr(_f32(gamma)), ptr(_f32(dgamma)), ptr(_f32(rstd)), gamma.numel(), bn_eps, ptr(eps),
+                                           ptr(deps), stream_ptr()), "sar_gin_eps_grad_bn_f32")
 
 
 # ------------------------------------------------------------------------------------------------ ST-PGCN projection graph convolution

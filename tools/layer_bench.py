@@ -1,7 +1,7 @@
 """The layer level measured (output kept as profiles/layers.txt):
 
-  1. the worst error of every case of tests/test_gpu_graph_sample.py and tests/test_gpu_layers.py (the tests print it; this tool
-     runs them and keeps those lines);
+  1. the worst error of every case of tests/test_gpu_graph_sample.py, tests/test_gpu_layers.py, tests/test_gpu_gin_sample.py and
+     tests/test_gpu_gin_layers.py (the tests print it; this tool runs them and keeps those lines);
   2. the per-sample adjacency contraction (csrc/graph_sample.hip) at the ST-PGCNP head shapes (N, F, V) = (128, 256, 512) and
      (128, 512, 256): time, achieved TFLOP/s, the fraction of the fp32 MFMA rate this box sustains (sar_amd.box.mfma) and the same
      product as torch.bmm on the SAME tensors -- the two interleaved in one process after a warm-up, several launches per timed
@@ -9,7 +9,11 @@
   3. one SpatioTemporalGraphConv forward + backward at (128, 64, 300, 25), the engine's block forward + backward on the same CN
      tensors (no boundary conversion, no parameter copies), and the two boundary conversions alone;
   4. what the compiler reports for each instance of the kernel (registers, spills, LDS, waves per SIMD): graph_sample.hip compiled
-     once more with the Makefile's flags and -Rpass-analysis=kernel-resource-usage, the object thrown away.
+     once more with the Makefile's flags and -Rpass-analysis=kernel-resource-usage, the object thrown away;
+  5. the graph isomorphism aggregation (sar_gin_sample_fwd_f32: the contraction with the self term (1 + eps) x in its epilogue) at
+     (N, F, V) = (128, 256, 512), (128, 16, 512) and (128, 64, 25) against the composition the code offered before it -- A + diag(1 + eps)
+     formed by torch, then sar_graph_sample_fwd_f32 -- and against sar_graph_sample_fwd_f32 alone, on the same tensors, interleaved as
+     in 2; and sar_gin_sample_eps_grad_f32 against its HBM floor of 2 F N V 4 bytes.
 
     python tools/layer_bench.py [--reps 10] [--no-errors] [--no-resources]
 """
@@ -29,6 +33,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "skeleton-action-recognition_amd")]
 from sar_amd import box, ops  # noqa: E402
 
 SHAPES = [(128, 256, 512), (128, 512, 256)]      # (N, F, V): the two ST-PGCNP heads
+GIN_SHAPES = [(128, 256, 512), (128, 16, 512), (128, 64, 25)]      # the head, few channels under a large graph, the skeleton graph
 
 
 def _ms(fn, inner):
@@ -56,7 +61,8 @@ def _interleaved(fns, reps, inner):
 def errors():
     print("== worst error per test case (printed by the tests)")
     out = subprocess.run([sys.executable, "-m", "pytest", "-q", "-s", "-m", "gpu", os.path.join(ROOT, "tests", "test_gpu_graph_sample.py"),
-                          os.path.join(ROOT, "tests", "test_gpu_layers.py")], capture_output=True, text=True, cwd=ROOT).stdout
+                          os.path.join(ROOT, "tests", "test_gpu_layers.py"), os.path.join(ROOT, "tests", "test_gpu_gin_sample.py"),
+                          os.path.join(ROOT, "tests", "test_gpu_gin_layers.py")], capture_output=True, text=True, cwd=ROOT).stdout
     for line in out.splitlines():
         line = line.lstrip(".")
         if "e-0" in line or "e-1" in line or " passed" in line or " failed" in line:
@@ -64,7 +70,8 @@ def errors():
 
 
 def resources():
-    print("== compiler's resource usage of csrc/graph_sample.hip (gs_kernel<WI, WJ, TM, TN, BK>: tile 32 WI TM x 32 WJ TN)")
+    print("== compiler's resource usage of csrc/graph_sample.hip (gs_kernel<WI, WJ, TM, TN, BK>: tile 32 WI TM x 32 WJ TN; SELF: the "
+          "gin instantiation; eg_*: the eps-gradient reduction)")
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         print("  hipcc not found: not measured")
@@ -81,8 +88,14 @@ def resources():
             continue
         text = m.group(1)
         if text.startswith("Function Name"):
-            t = re.search(r"gs_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", text)
-            print("  gs_kernel<%s>" % ", ".join(t.groups()) if t else "  " + text)
+            t = re.search(r"gs_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])E", text)
+            e = re.search(r"(eg_\w+_kernel)(?:ILb([01])E)?", text)
+            if t:
+                print("  gs_kernel<%s>%s" % (", ".join(t.groups()[:5]), "  SELF (gin)" if t.group(6) == "1" else ""))
+            elif e:
+                print("  %s%s" % (e.group(1), {None: "", "1": "<16 B per lane>", "0": "<element loads>"}[e.group(2)]))
+            else:
+                print("  " + text)
         elif any(k in text for k in keep):
             print("      " + text)
 
@@ -108,6 +121,32 @@ def kernels(dev, reps):
             (mo, lo, ho), (mb, lb, hb) = _interleaved([ours, theirs], reps, 5)
             print("%-16s %-9s %8.3f %8.1f %6.1f%% %8.3f-%-8.3f %8.3f %8.1f %8.3f-%-8.3f" % (
                 (N, F, V), name, mo, flops / mo / 1e9, 100.0 * flops / mo / 1e9 / peak, lo, ho, mb, flops / mb / 1e9, lb, hb))
+
+
+def gin(dev, reps):
+    print("== sar_gin_sample_fwd_f32 (self term in the epilogue) against torch's A + diag(1 + eps) then sar_graph_sample_fwd_f32, and "
+          "against sar_graph_sample_fwd_f32 alone; ms median (min-max)")
+    print("%-16s %-26s %-26s %-26s %-34s" % ("(N, F, V)", "fused", "A + diag by torch, then plain", "plain contraction alone",
+                                              "eps_grad (GB/s of 2 F N V 4 bytes)"))
+    g = torch.Generator().manual_seed(1)
+    for N, F, V in GIN_SHAPES:
+        x, A, d = (torch.randn(s, generator=g).to(dev) for s in ((N, F, V), (N, V, V), (N, F, V)))
+        cn = lambda t: t.permute(1, 0, 2).reshape(F, N * V).contiguous()
+        xc, dc = cn(x), cn(d)
+        out = torch.empty_like(xc)
+        eps = torch.tensor(0.3, device=dev)
+        deps = torch.empty((), device=dev)
+        eye = torch.eye(V, device=dev)
+        scratch = torch.empty(4 * 8192, device=dev)
+
+        def composed():
+            ops.graph_sample_fwd(xc, A + (1 + eps) * eye, out, F, V, N)
+        legs = [lambda: ops.gin_sample_fwd(xc, A, eps, out, F, V, N), composed, lambda: ops.graph_sample_fwd(xc, A, out, F, V, N),
+                lambda: ops.gin_sample_eps_grad(xc, dc, deps, F, V, N, scratch=scratch)]
+        res = _interleaved(legs, reps, 5)
+        cells = ["%.3f (%.3f-%.3f)" % r for r in res]
+        cells[3] += "  %.0f GB/s" % (2.0 * F * N * V * 4 / res[3][0] / 1e6)
+        print("%-16s %-26s %-26s %-26s %-34s" % ((str((N, F, V)),) + tuple(cells)))
 
 
 def block(dev, reps):
@@ -149,6 +188,7 @@ def main():
     dev = torch.device("cuda:0")
     kernels(dev, args.reps)
     block(dev, args.reps)
+    gin(dev, args.reps)
     if not args.no_errors:
         errors()
     if not args.no_resources:
