@@ -758,6 +758,9 @@ int sar_pgc_param_grad_f32(const float* colsum, const float* pooled, const float
  * is G = ceil(C/8) planes of ld >= n 16-byte units; unit (g, col) = the 8 bfloat16 channels 8g..8g+7 of that column,
  * channels >= C are zero.  Byte address of channel c, column n: 16*((c/8)*ld + n) + 2*(c%8).  All CN8 pointers are
  * 16-byte aligned; `ld` counts units per plane.  (This is the k-innermost MFMA operand image: csrc/cn8.h.)
+ * `ld` may exceed the live width n of every CN8 tensor (and of the one-byte-per-unit mask planes): units [n, ld) of a plane and
+ * planes beyond G are never read into a result and never written.  Every producer writes zeros to the pad lanes (channels >= C of
+ * the last plane) of the units it stores; every consumer may assume them zero (tests/test_gpu_cn8_guard_bands.py).
  *
  * sar_conv_gemm_cn8: the operators of sar_conv_gemm_f32 (same descriptor; src / out / aux are CN8 tensors passed through
  * the float* fields, ld_* in units; W is ignored) with the weights given as the packed bf16 image of

@@ -31,19 +31,30 @@ def _f32(t):
     return t
 
 
-def from_cn(x):
-    """fp32 CN matrix [C][n] -> CN8 (rounded to bfloat16, nearest even)"""
+def _rows(t):
+    """an fp32 CN matrix, possibly a view of rows with a leading dimension stride(0) >= n (the fp32 `ld` contract)"""
+    assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1), "need cuda float32 rows"
+    return t
+
+
+def from_cn(x, out=None):
+    """fp32 CN matrix [C][n] (row stride ld_x >= n) -> CN8 (rounded to bfloat16, nearest even).  out: a CN8 tensor (G, ld_out >= n, 8)
+    whose first n units per plane are written"""
     Cc, n = x.shape
-    out = empty(Cc, n, x.device)
-    check(L.load().sar_cn_to_cn8(ptr(_f32(x)), x.stride(0), ptr(out), n, Cc, n, stream_ptr()), "sar_cn_to_cn8")
+    if out is None:
+        out = empty(Cc, n, x.device)
+    assert _cn8(out).shape[0] == (Cc + 7) // 8
+    check(L.load().sar_cn_to_cn8(ptr(_rows(x)), x.stride(0), ptr(out), out.shape[1], Cc, n, stream_ptr()), "sar_cn_to_cn8")
     return out
 
 
-def to_cn(x8, channels):
-    """CN8 -> fp32 CN matrix [channels][n]"""
-    n = x8.shape[1]
-    out = torch.empty((channels, n), dtype=torch.float32, device=x8.device)
-    check(L.load().sar_cn8_to_cn(ptr(_cn8(x8)), n, ptr(out), n, channels, n, stream_ptr()), "sar_cn8_to_cn")
+def to_cn(x8, channels, n=None, out=None):
+    """CN8 -> fp32 CN matrix [channels][n].  n: the live width (default: ld = x8.shape[1]); out: fp32 rows of stride ld_out >= n"""
+    n = x8.shape[1] if n is None else n
+    if out is None:
+        out = torch.empty((channels, n), dtype=torch.float32, device=x8.device)
+    assert tuple(out.shape) == (channels, n)
+    check(L.load().sar_cn8_to_cn(ptr(_cn8(x8)), x8.shape[1], ptr(_rows(out)), out.stride(0), channels, n, stream_ptr()), "sar_cn8_to_cn")
     return out
 
 
@@ -144,59 +155,66 @@ def relu_mask(channels, n, device):
     return torch.empty(((channels + 7) // 8, n), dtype=torch.uint8, device=device)
 
 
-def bn_add_relu_fwd(u, sc, sh, res_kind, r, rsc, rsh, y, channels, mask=None):
+def bn_add_relu_fwd(u, sc, sh, res_kind, r, rsc, rsh, y, channels, mask=None, n=None):
+    """n: the live width (default: ld = u.shape[1]; every tensor, and the mask, has u's ld)"""
+    n = u.shape[1] if n is None else n
     if mask is not None:
         check(L.load().sar_bn_add_relu_fwd_mask_cn8(ptr(_cn8(u)), ptr(sc), ptr(sh), res_kind, ptr(_cn8(r)), ptr(rsc), ptr(rsh),
-                                                    ptr(_cn8(y)), ptr(mask), channels, u.shape[1], u.shape[1], stream_ptr()),
+                                                    ptr(_cn8(y)), ptr(mask), channels, n, u.shape[1], stream_ptr()),
               "sar_bn_add_relu_fwd_mask_cn8")
         return
     check(L.load().sar_bn_add_relu_fwd_cn8(ptr(_cn8(u)), ptr(sc), ptr(sh), res_kind, ptr(_cn8(r)), ptr(rsc), ptr(rsh), ptr(_cn8(y)),
-                                           channels, u.shape[1], u.shape[1], stream_ptr()), "sar_bn_add_relu_fwd_cn8")
+                                           channels, n, u.shape[1], stream_ptr()), "sar_bn_add_relu_fwd_cn8")
 
 
 _REDUCE_CHUNK = int(__import__("os").environ.get("SAR_BWD_REDUCE_CHUNK8", "8192"))     # units per workgroup of the BN-backward reduction
 
 
-def bn_add_relu_bwd_reduce(dy, y, u, r, channels, mu=None, mr=None, tail=None, mask=None):
-    """mask (relu_mask written by bn_add_relu_fwd): read instead of y"""
-    n = u.shape[1]
+def bn_add_relu_bwd_reduce(dy, y, u, r, channels, mu=None, mr=None, tail=None, mask=None, n=None):
+    """mask (relu_mask written by bn_add_relu_fwd): read instead of y.  n: the live width (default: ld = u.shape[1])"""
+    ld = u.shape[1]
+    n = ld if n is None else n
     nparts = max(1, min(4096, (n + _REDUCE_CHUNK - 1) // _REDUCE_CHUNK))
     partials = torch.empty((channels, nparts, 4), dtype=torch.float32, device=u.device)
     if mask is not None:
         assert tail is None
         check(L.load().sar_bn_add_relu_bwd_reduce_mask_cn8(ptr(_cn8(dy)), ptr(mask), ptr(_cn8(u)), ptr(_cn8(r)), ptr(mu), ptr(mr),
-                                                           ptr(partials), nparts, channels, n, n, stream_ptr()),
+                                                           ptr(partials), nparts, channels, n, ld, stream_ptr()),
               "sar_bn_add_relu_bwd_reduce_mask_cn8")
         return partials, nparts
     if tail is not None:      # ops.make_bn_tail: the last workgroup of every plane finalises its channels
         import ctypes
         check(L.load().sar_bn_add_relu_bwd_reduce_tail_cn8(ptr(_cn8(dy)), ptr(_cn8(y)), ptr(_cn8(u)), ptr(_cn8(r)), ptr(mu), ptr(mr),
-                                                           ptr(partials), nparts, channels, n, n, ctypes.byref(tail), stream_ptr()),
+                                                           ptr(partials), nparts, channels, n, ld, ctypes.byref(tail), stream_ptr()),
               "sar_bn_add_relu_bwd_reduce_tail_cn8")
         return partials, nparts
     check(L.load().sar_bn_add_relu_bwd_reduce_cn8(ptr(_cn8(dy)), ptr(_cn8(y)), ptr(_cn8(u)), ptr(_cn8(r)), ptr(mu), ptr(mr),
-                                                  ptr(partials), nparts, channels, n, n, stream_ptr()),
+                                                  ptr(partials), nparts, channels, n, ld, stream_ptr()),
           "sar_bn_add_relu_bwd_reduce_cn8")
     return partials, nparts
 
 
-def bn_add_relu_bwd_apply(dy, y, u, r, k, rk, du, dr, dz_out, channels, mask=None):
+def bn_add_relu_bwd_apply(dy, y, u, r, k, rk, du, dr, dz_out, channels, mask=None, n=None):
+    """n: the live width (default: ld = u.shape[1])"""
     rk = rk or (None, None, None)
-    n = u.shape[1]
+    ld = u.shape[1]
+    n = ld if n is None else n
     if mask is not None:
         check(L.load().sar_bn_add_relu_bwd_apply_mask_cn8(ptr(_cn8(dy)), ptr(mask), ptr(_cn8(u)), ptr(_cn8(r)), ptr(k[0]), ptr(k[1]),
                                                           ptr(k[2]), ptr(rk[0]), ptr(rk[1]), ptr(rk[2]), ptr(_cn8(du)), ptr(_cn8(dr)),
-                                                          ptr(_cn8(dz_out)), channels, n, n, stream_ptr()),
+                                                          ptr(_cn8(dz_out)), channels, n, ld, stream_ptr()),
               "sar_bn_add_relu_bwd_apply_mask_cn8")
         return
     check(L.load().sar_bn_add_relu_bwd_apply_cn8(ptr(_cn8(dy)), ptr(_cn8(y)), ptr(_cn8(u)), ptr(_cn8(r)), ptr(k[0]), ptr(k[1]),
                                                  ptr(k[2]), ptr(rk[0]), ptr(rk[1]), ptr(rk[2]), ptr(_cn8(du)), ptr(_cn8(dr)),
-                                                 ptr(_cn8(dz_out)), channels, n, n, stream_ptr()), "sar_bn_add_relu_bwd_apply_cn8")
+                                                 ptr(_cn8(dz_out)), channels, n, ld, stream_ptr()), "sar_bn_add_relu_bwd_apply_cn8")
 
 
-def affine2(a, b, k, out, channels):
-    n = a.shape[1]
-    check(L.load().sar_affine2_cn8(ptr(_cn8(a)), ptr(_cn8(b)), ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(_cn8(out)), channels, n, n,
+def affine2(a, b, k, out, channels, n=None):
+    """n: the live width (default: ld = a.shape[1])"""
+    ld = a.shape[1]
+    n = ld if n is None else n
+    check(L.load().sar_affine2_cn8(ptr(_cn8(a)), ptr(_cn8(b)), ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(_cn8(out)), channels, n, ld,
                                    stream_ptr()), "sar_affine2_cn8")
 
 

@@ -2,7 +2,8 @@
 import pytest
 import torch
 
-from util import MASK_FILL, NAN, SENTINEL, assert_flat_guards_untouched, assert_guards_untouched, guarded, guarded_flat
+from util import (MASK_FILL, NAN, SENTINEL, assert_cn8_guards_untouched, assert_cn8_pad_lanes_zero, assert_flat_guards_untouched,
+                  assert_guards_untouched, cn8_mask_bytes, cn8_units, cn8_values, guarded, guarded_cn8, guarded_cn8_mask, guarded_flat)
 
 CPU = torch.device("cpu")
 C, N = 5, 12
@@ -57,3 +58,99 @@ def test_flat_range():
             assert_flat_guards_untouched(w, 10, NAN)
     with pytest.raises(AssertionError):
         guarded_flat(10, SENTINEL, CPU, k=6)
+
+
+# ---- the CN8 helpers (planes of 16-byte units; tests/test_gpu_cn8_guard_bands.py)
+C8, N8 = 20, 13        # 3 planes, 4 pad lanes in the last one
+
+
+def _src8(C=C8, n=N8):
+    return (torch.arange(C * n, dtype=torch.float32).view(C, n) % 97 - 40).bfloat16().float() + 1      # bf16-exact, no zeros
+
+
+@pytest.mark.parametrize("pad", [0, 1, 67])
+def test_cn8_view_geometry(pad):
+    src = _src8()
+    view, whole = guarded_cn8(src, pad, NAN, CPU)
+    assert whole.dtype == torch.bfloat16 and whole.shape == (2 + 3 + 2, N8 + pad, 8) and whole.is_contiguous()
+    assert view.shape == (3, N8 + pad, 8) and view.is_contiguous() and view.data_ptr() % 16 == 0
+    assert view.data_ptr() == whole.data_ptr() + 2 * (N8 + pad) * 16
+    assert torch.equal(cn8_values(view[:, :N8], C8), src)
+    assert bool((view[2, :N8, C8 % 8:] == 0).all())                      # an input's pad lanes are zero
+    assert_cn8_pad_lanes_zero(view, C8, N8)
+    assert_cn8_guards_untouched(whole, C8, N8, NAN)
+    out, owhole = guarded_cn8((C8, N8), pad, SENTINEL, CPU)
+    assert bool((owhole == SENTINEL).all()) and out.shape == (3, N8 + pad, 8) and out.is_contiguous()
+    assert_cn8_guards_untouched(owhole, C8, N8, SENTINEL)
+    with pytest.raises(AssertionError, match="pad lane"):                  # an output's pad lanes start as the sentinel
+        assert_cn8_pad_lanes_zero(out, C8, N8)
+
+
+@pytest.mark.parametrize("fill,other", [(SENTINEL, 1.0), (NAN, 0.0)])
+@pytest.mark.parametrize("margin", ["front plane", "back plane", "pad column", "pad column of the last plane"])
+def test_cn8_one_flipped_guard_unit_is_seen(fill, other, margin):
+    pad = 67
+    view, whole = guarded_cn8((C8, N8), pad, fill, CPU)
+    view[:, :N8] = 3                                                     # the live region may hold anything
+    assert_cn8_guards_untouched(whole, C8, N8, fill)
+    g, c, j = {"front plane": (1, N8 - 1, 0), "back plane": (2 + 3, 0, 7), "pad column": (2 + 1, N8, 3),
+               "pad column of the last plane": (2 + 2, N8 + pad - 1, 5)}[margin]
+    whole[g, c, j] = other
+    with pytest.raises(AssertionError, match=r"plane %d, column %d\), lane %d .*overwritten.*\(1 elements" % (g - 2, c, j)):
+        assert_cn8_guards_untouched(whole, C8, N8, fill)
+
+
+def test_cn8_flipped_pad_lane_is_seen():
+    view, whole = guarded_cn8(_src8(), 1, NAN, CPU)
+    assert_cn8_pad_lanes_zero(view, C8, N8, "x")
+    view[2, 5, 6] = 0.5                                                  # channel 22 of a 20-channel tensor
+    with pytest.raises(AssertionError, match="pad lane 6 .channel 22 >= 20. of column 5"):
+        assert_cn8_pad_lanes_zero(view, C8, N8, "x")
+    view[2, 5, 6] = -0.0                                                 # a zero of either sign is a zero
+    assert_cn8_pad_lanes_zero(view, C8, N8, "x")
+    view[1, 5, 6] = float("inf")                                         # a live lane of a full plane is no pad lane
+    assert_cn8_pad_lanes_zero(view, C8, N8, "x")
+    full, _ = guarded_cn8((16, N8), 1, SENTINEL, CPU)                   # C % 8 == 0: there are none
+    assert_cn8_pad_lanes_zero(full, 16, N8, "x")
+
+
+def test_cn8_nan_fill_equals_itself_and_no_other_nan():
+    view, whole = guarded_cn8((C8, N8), 1, NAN, CPU)
+    assert bool(torch.isnan(whole).all())                                # the bf16 quiet NaN survives torch.full
+    assert_cn8_guards_untouched(whole, C8, N8, NAN)
+    whole.view(torch.int16)[0, 0, 0] ^= 1                                # still a NaN, another bit pattern
+    assert bool(torch.isnan(whole[0, 0, 0]))
+    with pytest.raises(AssertionError, match="overwritten"):
+        assert_cn8_guards_untouched(whole, C8, N8, NAN)
+
+
+@pytest.mark.parametrize("C", [3, 8, 20, 64])
+def test_cn8_host_layout_writer_round_trips_against_the_definition(C):
+    n = 29
+    x = torch.randn(C, n, generator=torch.Generator().manual_seed(C)).bfloat16().float()
+    units = cn8_units(x)
+    G = (C + 7) // 8
+    assert units.shape == (G, n, 8) and units.dtype == torch.bfloat16
+    for c in range(G * 8):                                               # unit (g, col)[j] = channel 8 g + j, zero beyond C
+        want = x[c] if c < C else torch.zeros(n)
+        assert torch.equal(units[c // 8, :, c % 8].float(), want), c
+    assert torch.equal(cn8_values(units, C), x)
+    with pytest.raises(AssertionError, match="representable"):
+        cn8_units(torch.full((C, n), 1.0 + 2.0 ** -12))
+
+
+def test_cn8_mask_bytes_and_their_guards():
+    keep = _src8() % 3 > 0
+    mb = cn8_mask_bytes(keep)
+    assert mb.shape == (3, N8) and mb.dtype == torch.uint8
+    for c in range(24):
+        assert torch.equal(((mb[c // 8] >> (c % 8)) & 1).bool(), keep[c] if c < C8 else torch.zeros(N8, dtype=torch.bool)), c
+    view, whole = guarded_cn8_mask(mb, 67, CPU)
+    assert whole.shape == (2 + 3 + 2, N8 + 67) and view.shape == (3, N8 + 67) and view.is_contiguous()
+    assert torch.equal(view[:, :N8], mb)
+    assert_guards_untouched(whole, (3, N8), MASK_FILL, 2, 2)
+    for r, c in ((1, 0), (5, N8 - 1), (3, N8), (4, N8 + 66)):
+        _, w = guarded_cn8_mask((3, N8), 67, CPU)
+        w[r, c] = 0
+        with pytest.raises(AssertionError, match="overwritten"):
+            assert_guards_untouched(w, (3, N8), MASK_FILL, 2, 2)

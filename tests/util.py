@@ -77,7 +77,9 @@ MASK_FILL = 0xA5         # padding of uint8 mask buffers
 
 def _bits(t):
     """the bit patterns of a tensor (a NaN equals itself)"""
-    return t.view(torch.int32) if t.dtype == torch.float32 else t
+    if t.dtype == torch.float32:
+        return t.view(torch.int32)
+    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t
 
 
 def guarded(src_or_shape, pad, fill, dev, front=4, back=2, dtype=torch.float32):
@@ -128,3 +130,85 @@ def assert_flat_guards_untouched(whole, n, fill, k=8, what=""):
         i = int(bad.nonzero()[0])
         raise AssertionError("%s: guard element %d of a %d-element range was overwritten with %r (%d in all)"
                              % (what, i - k, n, whole[i].item(), int(bad.sum())))
+
+
+# ---- guard bands of the bf16 (CN8) kernels: planes of 16-byte units (include/sar_hip.h "CN8"; tests/test_gpu_cn8_guard_bands.py)
+
+def cn8_units(src):
+    """(C, n) tensor of bf16-representable values -> (ceil(C/8), n, 8) bfloat16 on the host BY THE LAYOUT'S DEFINITION:
+    unit (g, col)[j] = channel 8 g + j, zero for channels >= C (not through sar_cn_to_cn8, which is itself under test)"""
+    C, n = src.shape
+    G = (C + 7) // 8
+    full = torch.zeros(G * 8, n, dtype=torch.float32)
+    full[:C] = src.detach().float().cpu()
+    assert torch.equal(full.bfloat16().float(), full), "cn8_units: values are not bfloat16-representable"
+    return full.view(G, 8, n).permute(0, 2, 1).contiguous().bfloat16()
+
+
+def cn8_values(units, C):
+    """the inverse of cn8_units on the host: (G, n, 8) units -> (C, n) float32 (exact)"""
+    G, n, _ = units.shape
+    return units.detach().float().cpu().permute(0, 2, 1).reshape(G * 8, n)[:C].contiguous()
+
+
+def guarded_cn8(src_or_shape, pad, fill, dev, front=2, back=2):
+    """(view, whole): `whole` is ONE contiguous bf16 allocation of (front + G + back) planes x (n + pad) units x 8 holding `fill`,
+    G = ceil(C/8); view = whole[front:front + G] is contiguous, of shape (G, ld = n + pad, 8): what ops8._cn8 accepts.  Given a
+    (C, n) tensor, the live units view[:, :n] hold it (cn8_units: pad lanes zero, the ABI's contract for an input); given a
+    shape (an output), the live units -- pad lanes included -- start as `fill`."""
+    src = src_or_shape if torch.is_tensor(src_or_shape) else None
+    C, n = src.shape if src is not None else src_or_shape
+    G = (C + 7) // 8
+    whole = torch.full((front + G + back, n + pad, 8), fill, dtype=torch.bfloat16, device=dev)
+    view = whole[front:front + G]
+    if src is not None:
+        view[:, :n] = cn8_units(src).to(dev)
+    return view, whole
+
+
+def guarded_cn8_mask(src_or_shape, pad, dev, front=2, back=2):
+    """(view, whole) of the CN8 mask layout -- one byte per unit, rows are planes: `whole` (front + G + back, n + pad) uint8 of
+    MASK_FILL, view = whole[front:front + G] (contiguous, (G, ld)); the live bytes view[:, :n] from a (G, n) uint8 tensor if given"""
+    src = src_or_shape if torch.is_tensor(src_or_shape) else None
+    G, n = src.shape if src is not None else src_or_shape
+    whole = torch.full((front + G + back, n + pad), MASK_FILL, dtype=torch.uint8, device=dev)
+    view = whole[front:front + G]
+    if src is not None:
+        view[:, :n] = src.to(dev)
+    return view, whole
+
+
+def cn8_mask_bytes(keep):
+    """(C, n) bool -> (ceil(C/8), n) bytes, bit j of byte (g, col) = channel 8 g + j (sar_bn_add_relu_fwd_mask_cn8's layout)"""
+    C, n = keep.shape
+    G = (C + 7) // 8
+    kb = torch.zeros(G * 8, n, dtype=torch.int32)
+    kb[:C] = keep.cpu().to(torch.int32)
+    return (kb.view(G, 8, n) << torch.arange(8, dtype=torch.int32).view(1, 8, 1)).sum(dim=1).to(torch.uint8).contiguous()
+
+
+def assert_cn8_guards_untouched(whole, C, n, fill, front=2, back=2, what=""):
+    """every unit of `whole` outside planes [front, front + G) x columns [0, n) still holds `fill`, bit for bit"""
+    G = (C + 7) // 8
+    assert whole.dim() == 3 and whole.shape[0] == front + G + back and whole.shape[1] >= n and whole.shape[2] == 8, \
+        "%s: not a guarded CN8 allocation" % what
+    want = _bits(torch.full((1,), fill, dtype=whole.dtype, device=whole.device))
+    bad = _bits(whole) != want
+    bad[front:front + G, :n] = False
+    if bool(bad.any()):
+        g, c, j = [int(v) for v in bad.nonzero()[0]]
+        raise AssertionError("%s: guard unit (plane %d, column %d), lane %d of a (%d planes, %d columns) view at plane %d, ld %d was "
+                             "overwritten with %r (%d elements in all)"
+                             % (what, g - front, c, j, G, n, front, whole.shape[1], whole[g, c, j].item(), int(bad.sum())))
+
+
+def assert_cn8_pad_lanes_zero(view, C, n, what=""):
+    """lanes C % 8 .. 7 of the last plane's live units (the channels >= C) are zero: what every consumer assumes"""
+    if C % 8 == 0:
+        return
+    lanes = view[(C + 7) // 8 - 1, :n, C % 8:]
+    bad = _bits(lanes) & 0x7fff != 0                 # (+0 or -0)
+    if bool(bad.any()):
+        c, j = [int(v) for v in bad.nonzero()[0]]
+        raise AssertionError("%s: pad lane %d (channel %d >= %d) of column %d holds %r, not zero (%d in all)"
+                             % (what, C % 8 + j, 8 * ((C + 7) // 8 - 1) + C % 8 + j, C, c, lanes[c, j].item(), int(bad.sum())))
