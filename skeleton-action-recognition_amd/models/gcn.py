@@ -11,12 +11,16 @@ load_state_dict), and are initialised with VarianceScaling(2, fan_out, truncated
 Inputs are contiguous float32 CUDA tensors in the reference's NCHW order; anything else raises ValueError before a launch.  Only
 the default einsum string of each layer is implemented; any other raises ValueError.
 
-Each layer is ONE torch.autograd.Function over sar_amd.ops:
-  * the 1x1 convolution is sar_conv_gemm_f32 (TEMPORAL, taps = 1) with its weight / data gradients;
-  * GraphConv contracts with the per-sample adjacency on csrc/graph_sample.hip (V <= 512);
-  * GraphConvTD takes the fused gather-list kernel (sar_conv_gemm_f32 GRAPH with GraphTables, exactly as the engine feeds it) when A
-    does not require a gradient, has 3 slices and at most 4 non-zeros per column and per row; any other A -- and AdjGraphConv
-    always -- takes the 1x1 product plus csrc/graph_dense.hip (V <= 32, K <= 8), which also yields dA.
+Each layer call is ONE torch.autograd.Function over sar_amd.ops:
+  * the 1x1 convolution is sar_conv_gemm_f32 (TEMPORAL, taps = 1) with its weight / data gradients, written once for every layer
+    of this file: _conv1x1_fwd / _conv1x1_wgrad / _conv1x1_dgrad;
+  * _ConvContractFn is the 1x1 product followed by a contraction with A, parameterised by the contraction's three kernels:
+    GraphConv contracts with the per-sample adjacency on csrc/graph_sample.hip (V <= 512);
+  * GraphConvTD takes the fused gather-list kernel (_GraphConvTDFusedFn: sar_conv_gemm_f32 GRAPH with GraphTables, exactly as the
+    engine feeds it; no intermediate) when A does not require a gradient, has 3 slices and at most 4 non-zeros per column and per
+    row; any other A -- and AdjGraphConv always -- takes _ConvContractFn with csrc/graph_dense.hip (V <= 32, K <= 8), which also
+    yields dA.
+Every layer's `kernel` / `bias` (and a GIN MLP layer's BatchNorm) live in one lazily built class, _Conv1x1Layer.
 
 The layers convert NCHW <-> the kernels' CN layout ([C][B*T*V]) at their boundary with the permute kernel.  A network composed
 of these layers pays that conversion PER LAYER; the whole-network engines (models/stgcn.py, stgin.py, stpgcn.py, stgcn_debug.py)
@@ -29,8 +33,11 @@ The graph isomorphism layers (models/gcn.py:54-163; `filters` is the list of MLP
 
 Both own the trainable scalar `epsilon` and the MLP(s) `mlp.{i}.*` / `mlps.{k}.{i}.*` (kernel, bias, gamma, beta; moving_mean and
 moving_var as buffers; BatchNorm eps 1e-3, momentum 0.99); see the classes.  training=False uses the moving statistics and is
-forward only.
+forward only.  The MLP arithmetic is written once, for K branches stacked along the channel axis (_mlp_forward / _mlp_backward):
+GraphIsoConv is its K = 1 case behind the per-sample aggregation, GraphIsoConvTD its K = kernel_size case behind the table
+expansion; the two autograd Functions hold only what is in front of the MLP and its gradient.
 """
+import collections
 import math
 
 import numpy as np
@@ -83,29 +90,35 @@ def variance_scaling_(kernel):
         kernel.copy_(w.to(torch.float32))
 
 
-# ---- the 1x1 convolution shared by the three layers: columns (B, T, V) of a CN matrix, V <= 64 (sar_conv_gemm_f32's limit)
-def _conv1x1_fwd(X, W, bias, geo):
+# ---- the 1x1 convolution shared by every layer: columns (B, T, V) of a CN matrix, V <= 64 (sar_conv_gemm_f32's limit); fp32 whatever
+# SAR_* split arithmetic is set (split=None).  `out` = rows of a caller's stacked matrix; **kw goes to the kernel as it is
+def _conv1x1_fwd(X, W, bias, geo, out=None, **kw):
+    """out (M, n) = W^T X + bias; kw: pro, pro_relu (BN + ReLU on the operand load), epi, partials_out (the statistics epilogue)"""
     C, M = W.shape
-    y = torch.empty((M, X.shape[1]), dtype=torch.float32, device=X.device)
-    ops.conv_gemm(L.SAR_CONV_TEMPORAL, X, y, W, 0, M, Kc=C, M=M, taps=1, stride=1, pad=0, bias=bias, split=None, **geo)
-    return y
+    if out is None:
+        out = torch.empty((M, X.shape[1]), dtype=torch.float32, device=X.device)
+    ops.conv_gemm(L.SAR_CONV_TEMPORAL, X, out, W, 0, M, Kc=C, M=M, taps=1, stride=1, pad=0, bias=bias, split=None, **geo, **kw)
+    return out
 
 
-def _conv1x1_bwd(X, dy, W, geo, need_w, need_dx):
-    """(dW (C, M), dbias (M), dX), each None when not asked for: the weight and bias gradients are one launch, dX another"""
+def _conv1x1_wgrad(X, dy, geo, **kw):
+    """(dW (C M), dbias (M)) of X (C, n) and dy (M, n), one launch; kw: pro, pro_relu"""
+    C, M = X.shape[0], dy.shape[0]
+    flat = torch.empty(C * M + M, dtype=torch.float32, device=X.device)
+    ops.conv_wgrad(L.SAR_CONV_TEMPORAL, X, dy, flat, Kc=C, M=M, taps=1, stride=1, pad=0, w_stride_tap=0, w_stride_c=M, wsize=C * M,
+                   bsize=M, split=None, **geo, **kw)
+    return flat[:C * M], flat[C * M:]
+
+
+def _conv1x1_dgrad(dy, W, geo, out=None, **kw):
+    """out (C, n) = W dy; kw: epi, aux, aux_affine, aux_mean, partials_out (the masked gradient through a folded BN + ReLU)"""
     C, M = W.shape
-    dW = db = dX = None
-    if need_w:
-        flat = torch.empty(C * M + M, dtype=torch.float32, device=X.device)
-        ops.conv_wgrad(L.SAR_CONV_TEMPORAL, X, dy, flat, Kc=C, M=M, taps=1, stride=1, pad=0, w_stride_tap=0, w_stride_c=M,
-                       wsize=C * M, bsize=M, split=None, **geo)
-        dW, db = flat[:C * M], flat[C * M:]
-    if need_dx:
-        WT = torch.empty((M, C), dtype=torch.float32, device=X.device)
-        ops.transpose(W, WT, 1, C, M)
-        dX = torch.empty((C, X.shape[1]), dtype=torch.float32, device=X.device)
-        ops.conv_gemm(L.SAR_CONV_TEMPORAL, dy, dX, WT, 0, C, Kc=M, M=C, taps=1, stride=1, pad=0, transposed=True, split=None, **geo)
-    return dW, db, dX
+    WT = torch.empty((M, C), dtype=torch.float32, device=dy.device)
+    ops.transpose(W, WT, 1, C, M)
+    if out is None:
+        out = torch.empty((C, dy.shape[1]), dtype=torch.float32, device=dy.device)
+    ops.conv_gemm(L.SAR_CONV_TEMPORAL, dy, out, WT, 0, C, Kc=M, M=C, taps=1, stride=1, pad=0, transposed=True, split=None, **geo, **kw)
+    return out
 
 
 def _column_geometry(N, V):
@@ -114,72 +127,48 @@ def _column_geometry(N, V):
     return dict(B=N, V=vf, T_src=V // vf, T_out=V // vf)
 
 
-class _GraphConvFn(torch.autograd.Function):
+# (forward, data gradient, adjacency gradient) of the two contractions behind a 1x1 product, each called as op(in, A, out, *dims)
+# (the adjacency gradient as op(y, dout, dA, *dims))
+SAMPLE_CONTRACTION = (ops.graph_sample_fwd, ops.graph_sample_bwd_data, ops.graph_sample_dA)      # dims (F, V, N): A (N, V, V), V <= 512
+DENSE_CONTRACTION = (ops.graph_dense_fwd, ops.graph_dense_bwd_data, ops.graph_dense_dA)          # dims (K, F, V, B T): A (K, V, V)
+
+
+class _ConvContractFn(torch.autograd.Function):
+    """the 1x1 convolution, then `contraction` with A: GraphConv (SAMPLE_CONTRACTION), the dense path of GraphConvTD and AdjGraphConv
+    (DENSE_CONTRACTION, dA included).  F = the channels that leave the contraction, geo = the column geometry of the product"""
+
     @staticmethod
-    def forward(ctx, x, A, kernel, bias):
-        N, C, V = x.shape
-        F = bias.shape[0]
-        geo = _column_geometry(N, V)
+    def forward(ctx, x, A, kernel, bias, contraction, dims, F, geo):
+        C = x.shape[1]
         X = to_cn(x)
-        y = _conv1x1_fwd(X, kernel.view(C, F), bias, geo)
-        out = torch.empty_like(y)
-        ops.graph_sample_fwd(y, A, out, F, V, N)
+        y = _conv1x1_fwd(X, kernel.view(C, -1), bias, geo)
+        out = torch.empty((F, X.shape[1]), dtype=torch.float32, device=x.device)
+        contraction[0](y, A, out, *dims)
         ctx.save_for_backward(X, y, A, kernel)
-        ctx.geo, ctx.shape = geo, (N, C, V)
-        return from_cn(out, (N, F, V))
+        ctx.contraction, ctx.dims, ctx.geo, ctx.shape = contraction, dims, geo, tuple(x.shape)
+        return from_cn(out, (x.shape[0], F) + tuple(x.shape[2:]))
 
     @staticmethod
     def backward(ctx, dout):
         X, y, A, kernel = ctx.saved_tensors
-        N, C, V = ctx.shape
-        F = kernel.shape[-1]
-        need_x, need_A, need_k, need_b = ctx.needs_input_grad
+        _, bwd_data, adjacency_grad = ctx.contraction
+        C = ctx.shape[1]
+        need_x, need_A, need_k, need_b = ctx.needs_input_grad[:4]
         dc = to_cn(dout.contiguous())
-        dA = dW = db = dX = None
+        dA = dW = db = dx = None
         if need_A:
             dA = torch.empty_like(A)
-            ops.graph_sample_dA(y, dc, dA, F, V, N)
+            adjacency_grad(y, dc, dA, *ctx.dims)
         if need_x or need_k or need_b:       # (only A asks for a gradient: nothing below is launched)
-            dy = torch.empty_like(dc)
-            ops.graph_sample_bwd_data(dc, A, dy, F, V, N)
-            dW, db, dX = _conv1x1_bwd(X, dy, kernel.view(C, F), ctx.geo, need_k or need_b, need_x)
-        return (from_cn(dX, (N, C, V)) if dX is not None else None), dA, (dW.view(kernel.shape) if dW is not None else None), db
-
-
-class _GraphConvTDDenseFn(torch.autograd.Function):
-    """Conv2D(K F, 1x1) then the dense contraction with A (K, V, V): csrc/graph_dense.hip, dA included"""
-
-    @staticmethod
-    def forward(ctx, x, A, kernel, bias):
-        B, C, T, V = x.shape
-        K = A.shape[0]
-        F = bias.shape[0] // K
-        geo = dict(B=B, V=V, T_src=T, T_out=T)
-        X = to_cn(x)
-        y3 = _conv1x1_fwd(X, kernel.view(C, K * F), bias, geo)
-        g = torch.empty((F, X.shape[1]), dtype=torch.float32, device=x.device)
-        ops.graph_dense_fwd(y3, A, g, K, F, V, B * T)
-        ctx.save_for_backward(X, y3, A, kernel)
-        ctx.geo, ctx.shape = geo, (B, C, T, V)
-        return from_cn(g, (B, F, T, V))
-
-    @staticmethod
-    def backward(ctx, dout):
-        X, y3, A, kernel = ctx.saved_tensors
-        B, C, T, V = ctx.shape
-        K = A.shape[0]
-        F = kernel.shape[-1] // K
-        need_x, need_A, need_k, need_b = ctx.needs_input_grad
-        dg = to_cn(dout.contiguous())
-        dA = dW = db = dX = None
-        if need_A:
-            dA = torch.empty_like(A)
-            ops.graph_dense_dA(y3, dg, dA, K, F, V, B * T)
-        if need_x or need_k or need_b:
-            dy3 = torch.empty_like(y3)
-            ops.graph_dense_bwd_data(dg, A, dy3, K, F, V, B * T)
-            dW, db, dX = _conv1x1_bwd(X, dy3, kernel.view(C, K * F), ctx.geo, need_k or need_b, need_x)
-        return (from_cn(dX, (B, C, T, V)) if dX is not None else None), dA, (dW.view(kernel.shape) if dW is not None else None), db
+            dy = torch.empty_like(y)
+            bwd_data(dc, A, dy, *ctx.dims)
+            W = kernel.view(C, -1)
+            if need_k or need_b:
+                dW, db = _conv1x1_wgrad(X, dy, ctx.geo)
+                dW = dW.view(kernel.shape)
+            if need_x:
+                dx = from_cn(_conv1x1_dgrad(dy, W, ctx.geo), ctx.shape)
+        return dx, dA, dW, db, None, None, None, None
 
 
 class _GraphConvTDFusedFn(torch.autograd.Function):
@@ -225,22 +214,36 @@ class _GraphConvTDFusedFn(torch.autograd.Function):
 
 
 class _Conv1x1Layer(torch.nn.Module):
-    """`kernel` / `bias` in the Keras layout, created on the first call (or by load_state_dict)"""
+    """Conv(out_channels, 1x1) [-> BatchNormalization(axis=1), has_bn]: `kernel` / `bias` in the Keras layout, with a BatchNorm also
+    `gamma` / `beta` and the buffers `moving_mean` / `moving_var`; created on the first call (or by load_state_dict)"""
 
-    def __init__(self, out_channels, kernel_rank):
+    def __init__(self, out_channels, kernel_rank, has_bn=False):
         super().__init__()
-        self.out_channels, self._kernel_rank = int(out_channels), kernel_rank
+        self.out_channels, self._kernel_rank, self.has_bn = int(out_channels), kernel_rank, bool(has_bn)
         self.register_parameter("kernel", None)
         self.register_parameter("bias", None)
+        if self.has_bn:
+            self.register_parameter("gamma", None)
+            self.register_parameter("beta", None)
+            self.register_buffer("moving_mean", None)
+            self.register_buffer("moving_var", None)
 
     def build(self, in_channels, device):
         if self.kernel is None:
-            shape = (1,) * (self._kernel_rank - 2) + (int(in_channels), self.out_channels)
+            f = self.out_channels
+            new = lambda fill: torch.full((f,), fill, dtype=torch.float32, device=device)
+            shape = (1,) * (self._kernel_rank - 2) + (int(in_channels), f)
             self.kernel = torch.nn.Parameter(torch.empty(shape, dtype=torch.float32, device=device))
-            self.bias = torch.nn.Parameter(torch.zeros(self.out_channels, dtype=torch.float32, device=device))
             variance_scaling_(self.kernel)
+            self.bias = torch.nn.Parameter(new(0.0))
+            if self.has_bn:
+                self.gamma, self.beta = torch.nn.Parameter(new(1.0)), torch.nn.Parameter(new(0.0))
+                self.moving_mean, self.moving_var = new(0.0), new(1.0)
         elif self.kernel.shape[-2] != in_channels:
             raise ValueError("the layer was built for %d input channels, got %d" % (self.kernel.shape[-2], in_channels))
+
+    def tensors(self):
+        return [self.kernel, self.bias] + ([self.gamma, self.beta] if self.has_bn else [])
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         k = state_dict.get(prefix + "kernel")
@@ -266,12 +269,20 @@ class GraphConv(_Conv1x1Layer):
         if N * V >= 1 << 22:
             raise ValueError("N * V = %d columns: the 1x1 product is built for fewer than 2^22" % (N * V))
         self.build(C, x.device)
-        return _GraphConvFn.apply(x, A, self.kernel, self.bias), A
+        return _ConvContractFn.apply(x, A, self.kernel, self.bias, SAMPLE_CONTRACTION, (self.out_channels, V, N), self.out_channels,
+                                     _column_geometry(N, V)), A
 
 
 def _dense_limits(K, V):
     if V > 32 or K > 8:
         raise ValueError("the dense adjacency contraction is built for V <= 32 and K <= 8 (got V = %d, K = %d)" % (V, K))
+
+
+def _conv_then_dense(layer, x, A):
+    """Conv2D(K F, 1x1) of `layer`, then the dense contraction with A (K, V, V): csrc/graph_dense.hip, dA included"""
+    B, C, T, V = x.shape
+    K, F = layer.kernel_size, layer.filters
+    return _ConvContractFn.apply(x, A, layer.kernel, layer.bias, DENSE_CONTRACTION, (K, F, V, B * T), F, dict(B=B, V=V, T_src=T, T_out=T))
 
 
 class GraphConvTD(_Conv1x1Layer):
@@ -312,7 +323,7 @@ class GraphConvTD(_Conv1x1Layer):
         self.build(C, x.device)
         if tables is not None:
             return _GraphConvTDFusedFn.apply(x, tables, self.kernel, self.bias), A
-        return _GraphConvTDDenseFn.apply(x, A, self.kernel, self.bias), A
+        return _conv_then_dense(self, x, A), A
 
 
 class AdjGraphConv(_Conv1x1Layer):
@@ -334,7 +345,7 @@ class AdjGraphConv(_Conv1x1Layer):
         if x.shape[3] != self.adjacency_matrix.shape[1]:
             raise ValueError("x has %d joints, adjacency_matrix %d" % (x.shape[3], self.adjacency_matrix.shape[1]))
         self.build(x.shape[1], x.device)
-        return _GraphConvTDDenseFn.apply(x, self.adjacency_matrix, self.kernel, self.bias)
+        return _conv_then_dense(self, x, self.adjacency_matrix)
 
 
 # ================================================================================================ graph isomorphism layers
@@ -348,37 +359,8 @@ class _BNState:
 
 
 def _rows(t, k, h):
-    return t[k * h:(k + 1) * h]
-
-
-class _GinMLPLayer(torch.nn.Module):
-    """one Conv(f, 1x1) [-> BatchNormalization(axis=1) -> ReLU] of a GIN MLP: `kernel` / `bias` in the Keras layout, `gamma` / `beta`
-    and the buffers `moving_mean` / `moving_var` where the layer has a BatchNorm; created by build()"""
-
-    def __init__(self, out_channels, kernel_rank, has_bn):
-        super().__init__()
-        self.out_channels, self._kernel_rank, self.has_bn = int(out_channels), kernel_rank, bool(has_bn)
-        self.register_parameter("kernel", None)
-        self.register_parameter("bias", None)
-        if self.has_bn:
-            self.register_parameter("gamma", None)
-            self.register_parameter("beta", None)
-            self.register_buffer("moving_mean", None)
-            self.register_buffer("moving_var", None)
-
-    def build(self, in_channels, device):
-        f = self.out_channels
-        new = lambda fill: torch.full((f,), fill, dtype=torch.float32, device=device)
-        self.kernel = torch.nn.Parameter(torch.empty((1,) * (self._kernel_rank - 2) + (int(in_channels), f), dtype=torch.float32,
-                                                     device=device))
-        variance_scaling_(self.kernel)
-        self.bias = torch.nn.Parameter(new(0.0))
-        if self.has_bn:
-            self.gamma, self.beta = torch.nn.Parameter(new(1.0)), torch.nn.Parameter(new(0.0))
-            self.moving_mean, self.moving_var = new(0.0), new(1.0)
-
-    def tensors(self):
-        return [self.kernel, self.bias] + ([self.gamma, self.beta] if self.has_bn else [])
+    """rows k h .. (k + 1) h of a stacked tensor; a single branch's rows are the tensor itself (no view is made)"""
+    return t if h == t.shape[0] else t[k * h:(k + 1) * h]
 
 
 def _check_gin_arguments(filters, activation, return_logits, einsum, default_einsum):
@@ -391,13 +373,13 @@ def _check_gin_arguments(filters, activation, return_logits, einsum, default_ein
 
 def _mlp(filters, kernel_rank, return_logits):
     last = len(filters) - 1
-    return torch.nn.ModuleList(_GinMLPLayer(f, kernel_rank, i < last or not return_logits) for i, f in enumerate(filters))
+    return torch.nn.ModuleList(_Conv1x1Layer(f, kernel_rank, i < last or not return_logits) for i, f in enumerate(filters))
 
 
-def _bn_forward(st, rows, result, count, layer, training, unbiased):
-    """BatchNorm of `layer` into rows `rows` of the (possibly stacked) state `st`: training, from the producer's statistics
-    (moving statistics updated); inference, from the moving statistics"""
-    view = lambda t: t if rows is None else _rows(t, rows, layer.out_channels)
+def _bn_forward(st, k, result, count, layer, training, unbiased):
+    """BatchNorm of `layer` into branch k's rows of the stacked state `st`: training, from the producer's statistics (moving
+    statistics updated); inference, from the moving statistics"""
+    view = lambda t: _rows(t, k, layer.out_channels)
     if training:
         ops.bn_finalize(result[0], result[1], layer.out_channels, count, BN_EPS, BN_MOMENTUM, unbiased, layer.gamma, layer.beta,
                         layer.moving_mean, layer.moving_var, view(st.mean), view(st.rstd), view(st.scale), view(st.shift))
@@ -405,135 +387,141 @@ def _bn_forward(st, rows, result, count, layer, training, unbiased):
         ops.bn_eval_affine(layer.gamma, layer.beta, layer.moving_mean, layer.moving_var, BN_EPS, view(st.scale), view(st.shift))
 
 
-def _bn_backward(st, rows, sums, count, layer):
-    """(dgamma, dbeta) of `layer`'s BatchNorm and k1..k3 of its backward apply pass, from (partials (f, nparts, 2), nparts) =
-    (sum dz, sum dz (a - mean)) per channel and partial"""
-    f = layer.out_channels
-    view = lambda t: t if rows is None else _rows(t, rows, f)
-    dg = torch.empty(2 * f, dtype=torch.float32, device=sums[0].device)
-    ops.bn_bwd_finalize(sums[0], sums[1], sums[1] * 2, 2, 0, 1, f, count, layer.gamma, view(st.mean), view(st.rstd), dg[:f], dg[f:],
+def _bn_backward(st, k, sums, count, f, gamma):
+    """(dgamma, dbeta) of the f-channel BatchNorm in branch k's rows of `st` and k1..k3 of its backward apply pass, from
+    (partials (f, nparts, 2), nparts) = (sum dz, sum dz (a - mean)) per channel and partial"""
+    view = lambda t: _rows(t, k, f)
+    dg = torch.empty(2 * f, dtype=torch.float32, device=gamma.device)
+    ops.bn_bwd_finalize(sums[0], sums[1], sums[1] * 2, 2, 0, 1, f, count, gamma, view(st.mean), view(st.rstd), dg[:f], dg[f:],
                         view(st.k1), view(st.k2), view(st.k3))
     return dg[:f], dg[f:]
 
 
-def _unpack(layers, params):
-    """the flat parameter list of Function.apply -> per layer (kernel, bias, gamma, beta) holders that read like the modules"""
-    out, i = [], 0
-    for l in layers:
-        n = 4 if l.has_bn else 2
-        out.append(params[i:i + n])
-        i += n
-    return out
+_MLPSaved = collections.namedtuple("_MLPSaved", "K geo n src acts states")      # one call's state between _mlp_forward and _mlp_backward
+
+
+def _mlp_forward(src, branches, geo, n, training, unbiased):
+    """The K = len(branches) GIN MLPs, stacked along the channel axis: branch k (a chain of _Conv1x1Layer, all chains of one shape)
+    reads rows k of src [K cin][n].  Every layer is the 1x1 product with the statistics epilogue (training), its BN + ReLU folded
+    into the next product's operand load; the last BN + ReLU and the sum over the branches are sar_gin_sum_fwd_f32.  The
+    element-wise passes are one launch for all branches; the BatchNorm finalisations run per branch on each layer's own gamma /
+    beta / moving statistics (`unbiased`: the moving variance's convention).  A last layer without a BatchNorm (return_logits) is
+    returned as it is, which a sum over branches cannot be.  -> (out [f_last][n], what _mlp_backward needs)"""
+    K, dev = len(branches), src.device
+    assert K == 1 or branches[0][-1].has_bn
+    new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
+    saved = _MLPSaved(K, geo, n, src, [], [])
+    cin, prev = src.shape[0] // K, None
+    for i, first in enumerate(branches[0]):
+        f, stats = first.out_channels, first.has_bn and training
+        a, st = new(K * f), _BNState(K * f, dev) if first.has_bn else None
+        if stats:
+            nparts = ops.conv_gemm_nparts(Kc=cin, M=f, **geo)
+            part = torch.empty((K * f, nparts, 2), dtype=torch.float32, device=dev)
+        for k, chain in enumerate(branches):
+            l = chain[i]
+            kw = dict(pro=(_rows(prev.scale, k, cin), _rows(prev.shift, k, cin)), pro_relu=True) if prev is not None else {}
+            if stats:
+                kw.update(epi=L.SAR_EPI_STATS, partials_out=_rows(part, k, f))
+            _conv1x1_fwd(_rows(src, k, cin), l.kernel.view(cin, f), l.bias, geo, out=_rows(a, k, f), **kw)
+            if l.has_bn:
+                _bn_forward(st, k, (_rows(part, k, f), nparts) if stats else None, n, l, training, unbiased)
+        saved.acts.append(a), saved.states.append(st)
+        src, cin, prev = a, f, st
+    out = src
+    if prev is not None:
+        out = new(cin)
+        ops.gin_sum_fwd(src, prev.scale, prev.shift, K, out)
+    return out, saved
+
+
+def _mlp_backward(saved, params, da):
+    """Backward of _mlp_forward (training): `params` = what the layers' tensors() gave, branch by branch and layer by layer, as
+    autograd saved them; da = the gradient of `out` (CN).  -> (the gradient of the stacked source, the gradients in the order of
+    `params`).  Layer i of branch k owns the slots 4 (k depth + i) .. + 3 = kernel, bias, gamma, beta: only the last layer of a
+    single branch may lack the last two, and nothing follows it."""
+    K, geo, n, src0, acts, states = saved
+    depth, dev = len(acts), da.device
+    new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
+    at = lambda k, i: 4 * (k * depth + i)
+    grads = [None] * len(params)
+    st, a = states[-1], acts[-1]
+    if st is not None:                        # the last BN + ReLU (and the sum over the branches)
+        f = a.shape[0] // K
+        sums = ops.gin_bwd_reduce(da, a, st.scale, st.shift, st.mean, K)
+        for k in range(K):
+            j = at(k, depth - 1)
+            grads[j + 2], grads[j + 3] = _bn_backward(st, k, (_rows(sums[0], k, f), sums[1]), n, f, params[j + 2])
+        dz = new(K * f)
+        ops.gin_bwd_apply(da, a, st.scale, st.shift, (st.k1, st.k2, st.k3), K, dz)
+        da = dz
+    for i in range(depth - 1, -1, -1):
+        f = acts[i].shape[0] // K
+        src, pst = (acts[i - 1], states[i - 1]) if i else (src0, None)
+        cin = src.shape[0] // K
+        dsrc = new(K * cin)
+        if i:
+            npm = ops.conv_gemm_nparts(Kc=f, M=cin, transposed=True, epi=L.SAR_EPI_MASK, **geo)
+            pm = torch.empty((K * cin, npm, 2), dtype=torch.float32, device=dev)
+        for k in range(K):
+            j, s_k, da_k = at(k, i), _rows(src, k, cin), _rows(da, k, f)
+            pro = (_rows(pst.scale, k, cin), _rows(pst.shift, k, cin)) if i else None
+            dW, grads[j + 1] = _conv1x1_wgrad(s_k, da_k, geo, pro=pro, pro_relu=pro is not None)
+            grads[j] = dW.view(params[j].shape)
+            # through the hidden BN + ReLU: masked data gradient + BatchNorm-backward sums
+            mask = dict(epi=L.SAR_EPI_MASK, aux=s_k, aux_affine=pro, aux_mean=_rows(pst.mean, k, cin),
+                        partials_out=_rows(pm, k, cin)) if i else {}
+            _conv1x1_dgrad(da_k, params[j].view(cin, f), geo, out=_rows(dsrc, k, cin), **mask)
+            if i:
+                jp = at(k, i - 1)
+                grads[jp + 2], grads[jp + 3] = _bn_backward(pst, k, (_rows(pm, k, cin), npm), n, cin, params[jp + 2])
+        if i:
+            ops.affine2(dsrc, src, (pst.k1, pst.k2, pst.k3), dsrc)
+        da = dsrc
+    return da, grads
 
 
 class _GraphIsoConvFn(torch.autograd.Function):
-    """GraphIsoConv as one node: the fused aggregation (csrc/graph_sample.hip, SELF), the MLP as 1x1 conv-GEMMs with the statistics
-    epilogue and each hidden BN + ReLU folded into the next product's operand load, the last BN + ReLU as sar_gin_sum_fwd_f32 (K = 1).
-    Everything backward needs is kept in ctx."""
+    """GraphIsoConv as one node: the fused aggregation (csrc/graph_sample.hip, SELF), then the MLP as _mlp_forward's single branch
+    (rows = the whole tensor).  Everything backward needs is kept in ctx."""
 
     @staticmethod
     def forward(ctx, x, A, layer, training, eps, *params):
         N, C, V = x.shape
-        n, dev = N * V, x.device
-        mlp = list(layer.mlp)
-        geo = dict(taps=1, stride=1, pad=0, split=None, **_column_geometry(N, V))
-        new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
         X = to_cn(x)
-        agg = new(C)
+        agg = torch.empty_like(X)
         ops.gin_sample_fwd(X, A, eps, agg, C, V, N)
-        acts, states, src, pro, cin = [], [], agg, None, C
-        for l in mlp:
-            f = l.out_channels
-            a = new(f)
-            res = ops.conv_gemm(L.SAR_CONV_TEMPORAL, src, a, l.kernel.view(cin, f), 0, f, Kc=cin, M=f, bias=l.bias, pro=pro,
-                                pro_relu=pro is not None, epi=L.SAR_EPI_STATS if (l.has_bn and training) else L.SAR_EPI_NONE, **geo)
-            st = None
-            if l.has_bn:
-                st = _BNState(f, dev)
-                _bn_forward(st, None, res, n, l, training, False)      # Keras' non-fused 3-D path: biased moving variance
-                pro = (st.scale, st.shift)
-            acts.append(a), states.append(st)
-            src, cin = a, f
-        out = src
-        if mlp[-1].has_bn:
-            out = new(cin)
-            ops.gin_sum_fwd(src, pro[0], pro[1], 1, out)
+        # Keras' non-fused 3-D path: biased moving variance
+        out, ctx.mlp = _mlp_forward(agg, layer._all_layers(), _column_geometry(N, V), N * V, training, False)
         ctx.save_for_backward(A, eps, *params)
-        ctx.layers, ctx.training, ctx.geo, ctx.shape = mlp, training, geo, (N, C, V)
-        ctx.X, ctx.agg, ctx.acts, ctx.states = X, agg, acts, states
-        return from_cn(out, (N, cin, V))
+        ctx.training, ctx.X = training, X
+        return from_cn(out, (N, out.shape[0], V))
 
     @staticmethod
     def backward(ctx, dout):
         if not ctx.training:
             raise RuntimeError("backward through GraphIsoConv(x, A, training=False) is not supported (inference path)")
         A, eps = ctx.saved_tensors[:2]
-        P = _unpack(ctx.layers, ctx.saved_tensors[2:])
-        mlp, geo, (N, C, V), acts, states = ctx.layers, ctx.geo, ctx.shape, ctx.acts, ctx.states
-        n, dev = N * V, dout.device
-        new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
-        grads = [None] * len(ctx.saved_tensors[2:])
-        base = [sum(4 if l.has_bn else 2 for l in mlp[:i]) for i in range(len(mlp))]
-        da = to_cn(dout.contiguous())
-        last = len(mlp) - 1
-        if mlp[last].has_bn:                  # the last BN + ReLU
-            st, a = states[last], acts[last]
-            sums = ops.gin_bwd_reduce(da, a, st.scale, st.shift, st.mean, 1)
-            grads[base[last] + 2], grads[base[last] + 3] = _bn_backward(st, None, sums, n, _Holder(mlp[last], P[last]))
-            dz = new(a.shape[0])
-            ops.gin_bwd_apply(da, a, st.scale, st.shift, (st.k1, st.k2, st.k3), 1, dz)
-            da = dz
-        for i in range(last, -1, -1):
-            l, f = mlp[i], mlp[i].out_channels
-            src = acts[i - 1] if i else ctx.agg
-            cin = src.shape[0]
-            pst = states[i - 1] if i else None
-            pro = (pst.scale, pst.shift) if i else None
-            W = P[i][0].view(cin, f)
-            flat = torch.empty(cin * f + f, dtype=torch.float32, device=dev)
-            ops.conv_wgrad(L.SAR_CONV_TEMPORAL, src, da, flat, Kc=cin, M=f, pro=pro, pro_relu=pro is not None, w_stride_tap=0,
-                           w_stride_c=f, wsize=cin * f, bsize=f, **geo)
-            grads[base[i]], grads[base[i] + 1] = flat[:cin * f].view(P[i][0].shape), flat[cin * f:]
-            WT = torch.empty((f, cin), dtype=torch.float32, device=dev)
-            ops.transpose(W, WT, 1, cin, f)
-            dsrc = new(cin)
-            if i:                             # through the hidden BN + ReLU: masked data gradient + BatchNorm-backward sums
-                sums = ops.conv_gemm(L.SAR_CONV_TEMPORAL, da, dsrc, WT, 0, cin, Kc=f, M=cin, transposed=True, epi=L.SAR_EPI_MASK,
-                                     aux=src, aux_affine=pro, aux_mean=pst.mean, **geo)
-                grads[base[i - 1] + 2], grads[base[i - 1] + 3] = _bn_backward(pst, None, sums, n, _Holder(mlp[i - 1], P[i - 1]))
-                ops.affine2(dsrc, src, (pst.k1, pst.k2, pst.k3), dsrc)
-            else:
-                ops.conv_gemm(L.SAR_CONV_TEMPORAL, da, dsrc, WT, 0, cin, Kc=f, M=cin, transposed=True, **geo)
-            da = dsrc
+        C, (N, V) = ctx.X.shape[0], A.shape[:2]
+        da, grads = _mlp_backward(ctx.mlp, ctx.saved_tensors[2:], to_cn(dout.contiguous()))
         need_x, need_A, _, _, need_eps = ctx.needs_input_grad[:5]
         dx = dA = deps = None
         if need_eps:
-            deps = torch.empty((), dtype=torch.float32, device=dev)
+            deps = torch.empty((), dtype=torch.float32, device=da.device)
             ops.gin_sample_eps_grad(ctx.X, da, deps, C, V, N)
         if need_A:
             dA = torch.empty_like(A)
             ops.graph_sample_dA(ctx.X, da, dA, C, V, N)
         if need_x:
-            dX = new(C)
+            dX = torch.empty_like(ctx.X)
             ops.gin_sample_bwd_data(da, A, eps, dX, C, V, N)
             dx = from_cn(dX, (N, C, V))
         return (dx, dA, None, None, deps) + tuple(grads)
 
 
-class _Holder:
-    """a layer's shape with the parameter tensors autograd saved for this call"""
-
-    def __init__(self, layer, params):
-        self.out_channels = layer.out_channels
-        self.gamma = params[2] if layer.has_bn else None
-
-
 class _GinBase(torch.nn.Module):
-    def _all_layers(self):
-        raise NotImplementedError
-
-    def _first_kernel_key(self):
-        raise NotImplementedError
+    """`epsilon` and the MLP chains of _all_layers() (a subclass's), created on the first call or by load_state_dict, which finds the
+    input width in the state dict's entry _first_kernel (a subclass's)"""
 
     def build(self, in_channels, device):
         layers = self._all_layers()
@@ -548,10 +536,15 @@ class _GinBase(torch.nn.Module):
             raise ValueError("the layer was built for %d input channels, got %d" % (layers[0][0].kernel.shape[-2], in_channels))
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        k = state_dict.get(prefix + self._first_kernel_key())
+        k = state_dict.get(prefix + self._first_kernel)
         if self.epsilon is None and k is not None:
             self.build(k.shape[-2], k.device if k.is_cuda else "cuda")
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def _call(self, fn, x, A, training):
+        self.build(x.shape[1], x.device)
+        params = [t for chain in self._all_layers() for l in chain for t in l.tensors()]
+        return fn.apply(x, A, self, bool(self.training if training is None else training), self.epsilon, *params), A
 
 
 class GraphIsoConv(_GinBase):
@@ -569,11 +562,10 @@ class GraphIsoConv(_GinBase):
         self.mlp = _mlp(self.filters, 3, self.return_logits)
         self.register_parameter("epsilon", None)
 
+    _first_kernel = "mlp.0.kernel"
+
     def _all_layers(self):
         return [list(self.mlp)]
-
-    def _first_kernel_key(self):
-        return "mlp.0.kernel"
 
     def forward(self, x, A, training=None):
         _require(x, 3, "x (N, C, V)")
@@ -583,19 +575,13 @@ class GraphIsoConv(_GinBase):
             raise ValueError("A must be (N, V, V) = (%d, %d, %d) with V <= 512, got %s" % (N, V, V, tuple(A.shape)))
         if N * V >= 1 << 22:
             raise ValueError("N * V = %d columns: the 1x1 products are built for fewer than 2^22" % (N * V))
-        if training is None:
-            training = self.training
-        self.build(C, x.device)
-        params = [t for l in self.mlp for t in l.tensors()]
-        return _GraphIsoConvFn.apply(x, A, self, bool(training), self.epsilon, *params), A
+        return self._call(_GraphIsoConvFn, x, A, training)
 
 
 class _GraphIsoConvTDFn(torch.autograd.Function):
     """GraphIsoConvTD as one node, composed from the kernels sar_amd/stgin.py runs for a dense adjacency: the table
-    [A_k^T.., (1 + eps) I] (sar_gin_adjacency_f32), x expanded to the K slices (sar_graph_dense_bwd_data_f32), the K MLPs stacked along
-    the channel axis ([K f][B T V] activations, K f-channel BatchNorm state per MLP layer: the element-wise passes are one launch for
-    all branches; the finalisations run per branch on each MLP's own gamma / beta / moving statistics), the last BN + ReLU + sum over
-    the branches (sar_gin_sum_fwd_f32).  Backward: the table's gradient (sar_graph_dense_dadj_f32 on (dz, x)) gives dA as its transpose
+    [A_k^T.., (1 + eps) I] (sar_gin_adjacency_f32), x expanded to the K slices (sar_graph_dense_bwd_data_f32), then the K MLPs as
+    _mlp_forward's stacked branches.  Backward: the table's gradient (sar_graph_dense_dadj_f32 on (dz, x)) gives dA as its transpose
     and d epsilon as the trace of its self slice, which sar_gin_eps_grad_bn_f32 then replaces by the well-conditioned closed form.
     Everything backward needs is kept in ctx."""
 
@@ -603,95 +589,26 @@ class _GraphIsoConvTDFn(torch.autograd.Function):
     def forward(ctx, x, A, layer, training, eps, *params):
         B, C, T, V = x.shape
         K, n, dev = layer.kernel_size, B * T * V, x.device
-        mlps = [list(m) for m in layer.mlps]
-        depth = len(mlps[0])
-        geo = dict(B=B, V=V, T_src=T, T_out=T, taps=1, stride=1, pad=0)
-        new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
         X = to_cn(x)
         table = torch.empty((K, V, V), dtype=torch.float32, device=dev)
         escale = torch.empty(C, dtype=torch.float32, device=dev)
         ops.gin_adjacency(A, eps, table, escale)
-        z = new(K * C)                                          # z[k C + c] = x[c] . A_k, the self slice (1 + eps) x[c]
+        z = torch.empty((K * C, n), dtype=torch.float32, device=dev)      # z[k C + c] = x[c] . A_k, the self slice (1 + eps) x[c]
         ops.graph_dense_bwd_data(X, table, z, K, C, V, B * T)
-        acts, states, src, cin, prev = [], [], z, C, None
-        for i in range(depth):
-            f = mlps[0][i].out_channels
-            a, st = new(K * f), _BNState(K * f, dev)
-            part = nparts = None
-            if training:
-                nparts = ops.conv_gemm_nparts(Kc=cin, M=f, **geo)
-                part = torch.empty((K * f, nparts, 2), dtype=torch.float32, device=dev)
-            for k in range(K):
-                l = mlps[k][i]
-                ops.conv_gemm(L.SAR_CONV_TEMPORAL, _rows(src, k, cin), _rows(a, k, f), l.kernel.view(cin, f), 0, f, Kc=cin, M=f,
-                              bias=l.bias, pro=(_rows(prev.scale, k, cin), _rows(prev.shift, k, cin)) if prev else None,
-                              pro_relu=prev is not None, epi=L.SAR_EPI_STATS if training else L.SAR_EPI_NONE,
-                              partials_out=_rows(part, k, f) if training else None, split=None, **geo)
-                _bn_forward(st, k, (_rows(part, k, f), nparts) if training else None, n, l, training, True)
-            acts.append(a), states.append(st)
-            src, cin, prev = a, f, st
-        out = new(cin)
-        ops.gin_sum_fwd(src, prev.scale, prev.shift, K, out)
+        # the fused 4-D convention of the engines: unbiased moving variance
+        out, ctx.mlp = _mlp_forward(z, layer._all_layers(), dict(B=B, V=V, T_src=T, T_out=T), n, training, True)
         ctx.save_for_backward(A, eps, *params)
-        ctx.mlps, ctx.training, ctx.geo, ctx.shape, ctx.K = mlps, training, geo, (B, C, T, V), K
-        ctx.X, ctx.z, ctx.table, ctx.acts, ctx.states = X, z, table, acts, states
-        return from_cn(out, (B, cin, T, V))
+        ctx.training, ctx.shape, ctx.X, ctx.table = training, (B, C, T, V), X, table
+        return from_cn(out, (B, out.shape[0], T, V))
 
     @staticmethod
     def backward(ctx, dout):
         if not ctx.training:
             raise RuntimeError("backward through GraphIsoConvTD(x, A, training=False) is not supported (inference path)")
         A, eps = ctx.saved_tensors[:2]
-        mlps, geo, (B, C, T, V), K, acts, states = ctx.mlps, ctx.geo, ctx.shape, ctx.K, ctx.acts, ctx.states
-        depth = len(mlps[0])
-        flat_layers = [l for m in mlps for l in m]              # the order of `params`: branch by branch
-        P = _unpack(flat_layers, ctx.saved_tensors[2:])
-        at = lambda k, i: k * depth + i
-        grads = [None] * (4 * len(flat_layers))
-        n, dev = B * T * V, dout.device
-        new = lambda rows: torch.empty((rows, n), dtype=torch.float32, device=dev)
-        ds = to_cn(dout.contiguous())
-        st, a = states[-1], acts[-1]
-        f = mlps[0][-1].out_channels
-        sums = ops.gin_bwd_reduce(ds, a, st.scale, st.shift, st.mean, K)
-        for k in range(K):
-            j = at(k, depth - 1)
-            grads[4 * j + 2], grads[4 * j + 3] = _bn_backward(st, k, (_rows(sums[0], k, f), sums[1]), n, _Holder(mlps[k][-1], P[j]))
-        da = new(K * f)
-        ops.gin_bwd_apply(ds, a, st.scale, st.shift, (st.k1, st.k2, st.k3), K, da)
-        for i in range(depth - 1, -1, -1):
-            f = mlps[0][i].out_channels
-            src = acts[i - 1] if i else ctx.z
-            cin = src.shape[0] // K
-            pst = states[i - 1] if i else None
-            dsrc = new(K * cin)
-            pm = npm = None
-            if i:
-                npm = ops.conv_gemm_nparts(Kc=f, M=cin, transposed=True, epi=L.SAR_EPI_MASK, **geo)
-                pm = torch.empty((K * cin, npm, 2), dtype=torch.float32, device=dev)
-            for k in range(K):
-                j = at(k, i)
-                pro = (_rows(pst.scale, k, cin), _rows(pst.shift, k, cin)) if i else None
-                W = P[j][0].view(cin, f)
-                flat = torch.empty(cin * f + f, dtype=torch.float32, device=dev)
-                ops.conv_wgrad(L.SAR_CONV_TEMPORAL, _rows(src, k, cin), _rows(da, k, f), flat, Kc=cin, M=f, pro=pro,
-                               pro_relu=pro is not None, w_stride_tap=0, w_stride_c=f, wsize=cin * f, bsize=f, split=None, **geo)
-                grads[4 * j], grads[4 * j + 1] = flat[:cin * f].view(P[j][0].shape), flat[cin * f:]
-                WT = torch.empty((f, cin), dtype=torch.float32, device=dev)
-                ops.transpose(W, WT, 1, cin, f)
-                if i:
-                    ops.conv_gemm(L.SAR_CONV_TEMPORAL, _rows(da, k, f), _rows(dsrc, k, cin), WT, 0, cin, Kc=f, M=cin, transposed=True,
-                                  epi=L.SAR_EPI_MASK, aux=_rows(src, k, cin), aux_affine=pro, aux_mean=_rows(pst.mean, k, cin),
-                                  partials_out=_rows(pm, k, cin), split=None, **geo)
-                    jp = at(k, i - 1)
-                    grads[4 * jp + 2], grads[4 * jp + 3] = _bn_backward(pst, k, (_rows(pm, k, cin), npm), n,
-                                                                        _Holder(mlps[k][i - 1], P[jp]))
-                else:
-                    ops.conv_gemm(L.SAR_CONV_TEMPORAL, _rows(da, k, f), _rows(dsrc, k, cin), WT, 0, cin, Kc=f, M=cin, transposed=True,
-                                  split=None, **geo)
-            if i:
-                ops.affine2(dsrc, src, (pst.k1, pst.k2, pst.k3), dsrc)
-            da = dsrc
+        params = ctx.saved_tensors[2:]
+        (B, C, T, V), K, dev = ctx.shape, ctx.table.shape[0], dout.device
+        da, grads = _mlp_backward(ctx.mlp, params, to_cn(dout.contiguous()))
         need_x, need_A, _, _, need_eps = ctx.needs_input_grad[:5]
         dx = dA = deps = None
         if need_A or need_eps:                 # the table's gradient: dA[k] is its transpose, d epsilon the trace of its self slice
@@ -708,11 +625,11 @@ class _GraphIsoConvTDFn(torch.autograd.Function):
                 # ... which fp32 leaves 1e-3 .. 1e-1 off: the self slice feeds Conv -> BatchNorm, whose output does not depend on the
                 # scale 1 + eps of its input but for BN_EPS, so d epsilon is what is left of terms that cancel to ~1e-3.  The closed
                 # form from that BatchNorm's backward (csrc/gin.hip) replaces the trace unless 1 + eps == 0
-                j0 = at(K - 1, 0)
-                ops.gin_eps_grad_bn(P[j0][2], grads[4 * j0 + 2], _rows(states[0].rstd, K - 1, mlps[K - 1][0].out_channels), BN_EPS, eps,
-                                    deps)
+                j0 = 4 * (K - 1) * len(ctx.mlp.acts)                 # the self branch's first layer: kernel, bias, gamma, beta
+                gamma = params[j0 + 2]
+                ops.gin_eps_grad_bn(gamma, grads[j0 + 2], _rows(ctx.mlp.states[0].rstd, K - 1, gamma.numel()), BN_EPS, eps, deps)
         if need_x:
-            dX = new(C)
+            dX = torch.empty_like(ctx.X)
             ops.graph_dense_fwd(da, ctx.table, dX, K, C, V, B * T)
             dx = from_cn(dX, (B, C, T, V))
         return (dx, dA, None, None, deps) + tuple(grads)
@@ -739,11 +656,10 @@ class GraphIsoConvTD(_GinBase):
         self.mlps = torch.nn.ModuleList(_mlp(self.filters, 4, False) for _ in range(kernel_size))
         self.register_parameter("epsilon", None)
 
+    _first_kernel = "mlps.0.0.kernel"
+
     def _all_layers(self):
         return [list(m) for m in self.mlps]
-
-    def _first_kernel_key(self):
-        return "mlps.0.0.kernel"
 
     def forward(self, x, A, training=None):
         _require(x, 4, "x (B, C, T, V)")
@@ -755,8 +671,4 @@ class GraphIsoConvTD(_GinBase):
         _dense_limits(K, V)
         if B * T * V >= 1 << 22:
             raise ValueError("B * T * V = %d columns: the convolutions are built for fewer than 2^22" % (B * T * V))
-        if training is None:
-            training = self.training
-        self.build(C, x.device)
-        params = [t for m in self.mlps for l in m for t in l.tensors()]
-        return _GraphIsoConvTDFn.apply(x, A, self, bool(training), self.epsilon, *params), A
+        return self._call(_GraphIsoConvTDFn, x, A, training)

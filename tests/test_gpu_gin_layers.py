@@ -11,7 +11,7 @@ the GPU).
 
 GraphIsoConvTD's d epsilon is compared like every other gradient, and it is the ill-conditioned one: the self slice (1 + eps) x feeds
 Conv -> BatchNorm, which cancels the scale of its input up to the BatchNorm's eps, so the float64 gradient is about 1e-3 of the terms
-that add up to it (3.3e-4 .. 4.2e-3 in the four cases here).  Float32 torch autograd on the CPU misses it by 3.3e-3, 6.5e-3, 3.8e-3
+that add up to it (3.3e-4 .. 4.2e-3 in the first four cases here).  Float32 torch autograd on the CPU misses it by 3.3e-3, 6.5e-3, 3.8e-3
 and 7.8e-2 in these cases, and so did the layer (4.1e-3, 2.4e-3, 5.3e-4, 7.6e-2) while it took d epsilon as the trace of the table
 gradient's self slice; the closed form from the first BatchNorm's backward (sar_gin_eps_grad_bn_f32) is what meets the bar."""
 import pytest
@@ -123,14 +123,18 @@ def test_graph_iso_conv(dev, name):
     against_the_reference(dev, "GraphIsoConv " + name, *iso_case(name, dev))
 
 
-TD_CASES = {"Graph().A[1:]": (3, "graph", False, 200), "random A, dA": (3, "random", True, 219),
-            "kernel_size 2": (2, "random", False, 221), "kernel_size 4": (4, "random", True, 231)}
+# the last three: cin != f in the second MLP layer (a swapped cin / f in a stacked-row view, a partials shape or a weight stride shows),
+# depth 1 and depth 3
+TD_CASES = {"Graph().A[1:]": ([12, 12], 3, "graph", False, 200), "random A, dA": ([12, 12], 3, "random", True, 219),
+            "kernel_size 2": ([12, 12], 2, "random", False, 221), "kernel_size 4": ([12, 12], 4, "random", True, 231),
+            "unequal widths": ([12, 8], 3, "random", True, 261), "one layer": ([8], 2, "random", False, 240),
+            "three layers": ([12, 8, 20], 2, "random", True, 240)}
 
 
 def td_case(name, device):
-    K, kind, A_grad, seed = TD_CASES[name]
-    layer = built(GraphIsoConvTD([12, 12], kernel_size=K), 16, device, seed)
-    x, dout = _randn(2, 16, 12, 25, seed=seed + 2), _randn(2, 12, 12, 25, seed=seed + 4)
+    filters, K, kind, A_grad, seed = TD_CASES[name]
+    layer = built(GraphIsoConvTD(filters, kernel_size=K), 16, device, seed)
+    x, dout = _randn(2, 16, 12, 25, seed=seed + 2), _randn(2, filters[-1], 12, 25, seed=seed + 4)
     A = torch.from_numpy(Graph().A[1:]).float() if kind == "graph" else 0.3 * _randn(K - 1, 25, 25, seed=seed + 3)
     return layer, x, A, dout, A_grad
 
