@@ -998,13 +998,14 @@ def _pack_split_conv2d(W, w_stride_tap, w_stride_c, Kc, M, arith, transposed):
 
 
 def conv2d_gemm(src, out, W, w_stride_tap, w_stride_c, *, epi=L.SAR_EPI_NONE, aux=None, aux_affine=None, aux_mean=None,
-                aux_even_pixels=False, ctx=None, split="default", packed=None, bounds=None, **geo):
+                aux_even_pixels=False, ctx=None, split="default", packed=None, bounds=None, kslab=None, **geo):
     """sar_conv2d_gemm_f32 -- or, with split="f16x3a" / "bf16x6" on the shapes conv2d_split_applicable() names, the fp32-accurate
     split arithmetic on the fp16 / bf16 matrix pipe (sar_conv2d_gemm_split; `packed` = the PackedSplitWeights image of the launch's
     view of the weights or None = pack here from W; bounds = (src_bound, w_bound) cells, None = computed here by device kernels).
     Returns (partials, nparts) when the epilogue reduces.  aux_even_pixels: SAR_C2D_AUX_EVEN_PIXELS
     (aux is the compact data gradient of the parallel 1x1 / stride 2 convolution, added at the even pixels only).
-    ctx: an L.Context whose side streams the call may fan out over (None: the current stream only)."""
+    ctx: an L.Context whose side streams the call may fan out over (None: the current stream only).
+    kslab: a callable nfloats -> flat float32 tensor that provides the K-split workspace (None: torch.empty here)."""
     lib = L.load()
     if split == "default":
         split = DEFAULT_SPLIT
@@ -1022,11 +1023,11 @@ def conv2d_gemm(src, out, W, w_stride_tap, w_stride_c, *, epi=L.SAR_EPI_NONE, au
     d.aux_mean = ptr(_f32(aux_mean))
     partials = None
     nparts = 0
-    kslab = None
     if split:      # small feature maps: workspace of the K-split (sar_hip.h), 0 bytes = not planned for this shape
         nb = lib.sar_conv2d_gemm_split_slab_bytes(C.byref(d))
         if nb > 0:
-            kslab = torch.empty(nb // 4, dtype=torch.float32, device=src.device)
+            kslab = kslab(nb // 4) if kslab is not None else torch.empty(nb // 4, dtype=torch.float32, device=src.device)
+            assert kslab.dtype == torch.float32 and kslab.is_contiguous() and kslab.numel() >= nb // 4
             d.slab = ptr(kslab)
     if epi in (L.SAR_EPI_STATS, L.SAR_EPI_MASK):
         nparts = lib.sar_conv2d_gemm_split_nparts(C.byref(d)) if split else lib.sar_conv2d_nparts(C.byref(d))

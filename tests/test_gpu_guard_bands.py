@@ -20,8 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import stgcn as O
-from util import (MASK_FILL, NAN, SENTINEL, assert_flat_guards_untouched, assert_guards_untouched, guarded, guarded_flat, rel_err,
-                  to_cn)
+from util import NAN, SENTINEL, Launch, drive, guarded, guarded_flat, mask_bytes, rejected, rel_err, to_cn
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5                      # the per-kernel bar (tests/test_gpu_stgcn_kernels.py)
@@ -40,109 +39,6 @@ def dev():
 def cn(x):
     """(B, C, T, V) or (B, C, H, W) -> CN matrix [C][B * rest]"""
     return x.permute(1, 0, 2, 3).reshape(x.shape[1], -1).contiguous()
-
-
-class Launch:
-    """the operands and results of one run of a case at one `pad`"""
-
-    def __init__(self, dev, pad):
-        self.dev, self.pad = dev, pad
-        self.outs, self.flats, self.masks, self.parts, self.refs = {}, {}, {}, {}, []
-
-    def inp(self, src):
-        """a (C, n) input as a guarded view, NaN all around"""
-        return guarded(src.float(), self.pad, NAN, self.dev, FRONT, BACK)[0]
-
-    def out(self, name, C, n):
-        view, whole = guarded((C, n), self.pad, SENTINEL, self.dev, FRONT, BACK)
-        self.outs[name] = (view, whole)
-        return view
-
-    def flat(self, name, n):
-        view, whole = guarded_flat(n, SENTINEL, self.dev, KFLAT)
-        self.flats[name] = (view, whole)
-        return view
-
-    def mask(self, name, C, n, keep=None):
-        """the (C, ld / 4) mask bytes of a (C, n) tensor of row stride ld = n + pad (ops.relu_mask's layout) with guard rows; the live
-        bytes are columns [0, n / 4): from `keep` (C, n) bool when given.  Returns the contiguous (C, ld / 4) tensor the ABI takes."""
-        whole = torch.full((FRONT + C + BACK, (n + self.pad) // 4), MASK_FILL, dtype=torch.uint8, device=self.dev)
-        rows = whole[FRONT:FRONT + C]
-        if keep is not None and n % 4 == 0:      # (rows that are no 4-element groups have no mask: the call is to be rejected)
-            rows[:, :n // 4] = mask_bytes(keep).to(self.dev)
-        self.masks[name] = (rows[:, :n // 4], whole)
-        return rows
-
-    def part(self, name, t, cols=None):
-        """a reduction partial allocated inside ops: checked finite (cols: the leading entries of the last axis that are defined)"""
-        self.parts[name] = t if cols is None else t[..., :cols]
-        return t
-
-    def ref(self, what, got, want, tol):
-        """got (a device tensor or a callable evaluated after the launches) against `want`: rel_err < tol, or bitwise when tol == 0"""
-        self.refs.append((what, got, want, tol))
-
-    def check(self):
-        self.check_guards()                                                                      # 3
-        for name, (view, _) in list(self.outs.items()) + list(self.flats.items()):                # 4
-            assert bool(torch.isfinite(view).all()), "%s (pad %d): not finite" % (name, self.pad)
-        for name, t in self.parts.items():
-            assert bool(torch.isfinite(t).all()), "partials %s (pad %d): not finite" % (name, self.pad)
-        for what, got, want, tol in self.refs:                                                   # 1
-            got = got() if callable(got) else got
-            want = want() if callable(want) else want
-            if tol == 0:
-                assert torch.equal(got.cpu(), want.cpu()), "%s (pad %d): not bitwise equal" % (what, self.pad)
-            else:
-                e = rel_err(got.cpu(), want.cpu())
-                print("%s (pad %d): %.2e" % (what, self.pad, e))
-                assert e < tol, "%s (pad %d): %.3e >= %.1e" % (what, self.pad, e, tol)
-
-    def check_guards(self):
-        for name, (view, whole) in self.outs.items():
-            assert_guards_untouched(whole, view.shape, SENTINEL, FRONT, BACK, "%s (pad %d)" % (name, self.pad))
-        for name, (view, whole) in self.masks.items():
-            assert_guards_untouched(whole, view.shape, MASK_FILL, FRONT, BACK, "mask %s (pad %d)" % (name, self.pad))
-        for name, (view, whole) in self.flats.items():
-            assert_flat_guards_untouched(whole, view.numel(), SENTINEL, KFLAT, "%s (pad %d)" % (name, self.pad))
-
-    def check_nothing_written(self):
-        """5: a rejected call launched nothing"""
-        for name, (_, whole) in list(self.outs.items()) + list(self.flats.items()):
-            assert bool((whole == SENTINEL).all()), "%s (pad %d): written by a rejected call" % (name, self.pad)
-
-
-def drive(dev, fn, pad, bitwise=True):
-    """run `fn` tight and with `pad`, apply the five assertions"""
-    tight, padded = Launch(dev, 0), Launch(dev, pad)
-    fn(tight)
-    fn(padded)
-    torch.cuda.synchronize()
-    tight.check()
-    padded.check()
-    # (a variant that a padded ld is rejected for has an output in the tight launch only)
-    assert set(tight.outs) >= set(padded.outs) and set(tight.flats) == set(padded.flats) and set(tight.masks) >= set(padded.masks)
-    if bitwise:                                                                                  # 2
-        for kind in ("outs", "flats", "masks"):
-            for name, (view, _) in getattr(padded, kind).items():
-                assert torch.equal(view, getattr(tight, kind)[name][0]), "%s: pad %d differs from the tight launch" % (name, pad)
-    return tight, padded
-
-
-def rejected(dev, fn, pad):
-    """the ABI does not take this leading dimension: the call raises and writes nothing"""
-    from sar_amd import _lib as L
-    launch = Launch(dev, pad)
-    with pytest.raises((L.SarError, AssertionError)):
-        fn(launch)
-    torch.cuda.synchronize()
-    launch.check_nothing_written()
-
-
-def mask_bytes(keep):
-    """(C, n) bool -> (C, n / 4) bytes, bit j = element 4 i + j (sar_bn_add_relu_fwd_mask_f32's layout)"""
-    C, n = keep.shape
-    return (keep.view(C, n // 4, 4).to(torch.int32) * torch.tensor([1, 2, 4, 8], dtype=torch.int32, device=keep.device)).sum(dim=2).to(torch.uint8)
 
 
 def _A():

@@ -2,8 +2,9 @@
 import pytest
 import torch
 
-from util import (MASK_FILL, NAN, SENTINEL, assert_cn8_guards_untouched, assert_cn8_pad_lanes_zero, assert_flat_guards_untouched,
-                  assert_guards_untouched, cn8_mask_bytes, cn8_units, cn8_values, guarded, guarded_cn8, guarded_cn8_mask, guarded_flat)
+from util import (MASK_FILL, NAN, SENTINEL, GuardedSlabs, Launch, assert_cn8_guards_untouched, assert_cn8_pad_lanes_zero,
+                  assert_flat_guards_untouched, assert_guards_untouched, cn8_mask_bytes, cn8_units, cn8_values, guarded, guarded_cn8,
+                  guarded_cn8_mask, guarded_flat)
 
 CPU = torch.device("cpu")
 C, N = 5, 12
@@ -154,3 +155,84 @@ def test_cn8_mask_bytes_and_their_guards():
         w[r, c] = 0
         with pytest.raises(AssertionError, match="overwritten"):
             assert_guards_untouched(w, (3, N8), MASK_FILL, 2, 2)
+
+
+# ---- the launch record and the guarded slabs of the weight gradients (tests/test_gpu_split_guard_bands.py)
+
+def _cpu_reduce(slab, nsplit, n, out):
+    out[:n] = slab[:nsplit, :n].sum(0)
+
+
+def test_guarded_slabs_geometry_and_reduction():
+    nsplit, n = 3, 10
+    out = torch.zeros(n)
+    batch = GuardedSlabs(CPU, _cpu_reduce)
+    slab = batch.slab(out, nsplit, n)
+    view, whole, _, _ = batch.items[0]
+    assert slab.shape == (nsplit, n) and slab.is_contiguous() and slab.data_ptr() == whole.data_ptr() + 32 and slab.data_ptr() % 16 == 0
+    assert whole.numel() == nsplit * n + 16 and bool(torch.isnan(slab).all()) and bool((whole[:8] == SENTINEL).all()) and bool((whole[-8:] == SENTINEL).all())
+    batch.check_guards()
+    batch.check_nothing_written()
+    with pytest.raises(AssertionError, match="never written"):
+        batch.check_finite()
+    slab.copy_(torch.arange(nsplit * n, dtype=torch.float32).view(nsplit, n))
+    batch.add(slab, nsplit, n, out)
+    assert torch.equal(out, torch.arange(n, dtype=torch.float32) * 3 + 30)
+    batch.check_finite()
+    batch.check_guards()
+    with pytest.raises(AssertionError, match="written by a rejected call"):
+        batch.check_nothing_written()
+    with pytest.raises(AssertionError, match="not a slab of this batch"):
+        batch.add(torch.zeros(nsplit, n), nsplit, n, out)
+
+
+@pytest.mark.parametrize("where", ["one element no workgroup wrote", "one element past the last slab", "one element in front of the first slab"])
+def test_guarded_slabs_see_a_missing_and_a_stray_write(where):
+    nsplit, n = 4, 6
+    out = torch.zeros(n)
+    batch = GuardedSlabs(CPU, _cpu_reduce)
+    slab = batch.slab(out, nsplit, n)
+    slab.fill_(1.0)
+    whole = batch.items[0][1]
+    if where == "one element no workgroup wrote":
+        slab[2, 5] = NAN
+        batch.add(slab, nsplit, n, out)
+        batch.check_guards()
+        assert not bool(torch.isfinite(out).all())                        # it reaches the reduced gradient
+        with pytest.raises(AssertionError, match="element 5 of slab 2 of a .4, 6. slab buffer was never written"):
+            batch.check_finite()
+        return
+    whole[8 + nsplit * n if where == "one element past the last slab" else 7] = 0.0
+    batch.check_finite()
+    with pytest.raises(AssertionError, match="overwritten"):
+        batch.check_guards()
+
+
+def test_launch_record_on_the_cpu():
+    class Wide(Launch):
+        IN_BACK = 16
+    g = Wide(CPU, 7)
+    x = g.inp(torch.ones(C, N))
+    assert x.stride(0) == N + 7 and x.storage_offset() == 4 * (N + 7) and x.untyped_storage().nbytes() == 4 * (4 + C + 16) * (N + 7)
+    out, flat = g.out("out", C, N), g.flat("flat", 9)
+    out.fill_(2.0)
+    flat.fill_(1.0)
+    g.ref("relative to max |want|", out, torch.full((C, N), 2.0 + 1e-5), 1e-5)
+    g.ref("relative to a stated scale", out, torch.full((C, N), 2.0 + 1e-3), 1e-5, scale=1000.0)
+    g.ref("bitwise", lambda: flat, torch.ones(9), 0)
+    g.check()
+    g.ref("too far", out, torch.full((C, N), 2.1), 1e-5)
+    with pytest.raises(AssertionError, match="too far"):
+        g.check()
+    g.refs.pop()
+    out[0, 0] = NAN
+    with pytest.raises(AssertionError, match="not finite"):
+        g.check()
+    out[0, 0] = 2.0
+    g.outs["out"][1][4 + C, 0] = 0.0                                       # the first guard row behind the output
+    with pytest.raises(AssertionError, match="overwritten"):
+        g.check()
+    with pytest.raises(AssertionError, match="written by a rejected call"):
+        g.check_nothing_written()
+    slabs = g.slab_batch(_cpu_reduce)
+    assert g.slabs == [slabs]

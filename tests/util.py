@@ -132,6 +132,165 @@ def assert_flat_guards_untouched(whole, n, fill, k=8, what=""):
                              % (what, i - k, n, whole[i].item(), int(bad.sum())))
 
 
+# ---- one guarded launch and its five assertions (tests/test_gpu_guard_bands.py states them; tests/test_gpu_split_guard_bands.py
+# runs the split-arithmetic kernels through the same ones)
+
+def mask_bytes(keep):
+    """(C, n) bool -> (C, n / 4) bytes, bit j = element 4 i + j (sar_bn_add_relu_fwd_mask_f32's layout)"""
+    C, n = keep.shape
+    return (keep.view(C, n // 4, 4).to(torch.int32) * torch.tensor([1, 2, 4, 8], dtype=torch.int32, device=keep.device)).sum(dim=2).to(torch.uint8)
+
+
+class Launch:
+    """the operands and results of one run of a case at one `pad`"""
+    FRONT, BACK, KFLAT = 4, 2, 8      # guard rows of every operand, guard elements of a flat range
+    IN_BACK = 2                       # guard rows behind an INPUT (a family whose stagers round the channel count up asks for more)
+
+    def __init__(self, dev, pad):
+        self.dev, self.pad = dev, pad
+        self.outs, self.flats, self.masks, self.parts, self.refs, self.slabs = {}, {}, {}, {}, [], []
+
+    def inp(self, src):
+        """a (C, n) input as a guarded view, NaN all around"""
+        return guarded(src.float(), self.pad, NAN, self.dev, self.FRONT, self.IN_BACK)[0]
+
+    def out(self, name, C, n):
+        view, whole = guarded((C, n), self.pad, SENTINEL, self.dev, self.FRONT, self.BACK)
+        self.outs[name] = (view, whole)
+        return view
+
+    def flat(self, name, n):
+        view, whole = guarded_flat(n, SENTINEL, self.dev, self.KFLAT)
+        self.flats[name] = (view, whole)
+        return view
+
+    def mask(self, name, C, n, keep=None):
+        """the (C, ld / 4) mask bytes of a (C, n) tensor of row stride ld = n + pad (ops.relu_mask's layout) with guard rows; the live
+        bytes are columns [0, n / 4): from `keep` (C, n) bool when given.  Returns the contiguous (C, ld / 4) tensor the ABI takes."""
+        whole = torch.full((self.FRONT + C + self.BACK, (n + self.pad) // 4), MASK_FILL, dtype=torch.uint8, device=self.dev)
+        rows = whole[self.FRONT:self.FRONT + C]
+        if keep is not None and n % 4 == 0:      # (rows that are no 4-element groups have no mask: the call is to be rejected)
+            rows[:, :n // 4] = mask_bytes(keep).to(self.dev)
+        self.masks[name] = (rows[:, :n // 4], whole)
+        return rows
+
+    def part(self, name, t, cols=None):
+        """a reduction partial allocated inside ops: checked finite (cols: the leading entries of the last axis that are defined)"""
+        self.parts[name] = t if cols is None else t[..., :cols]
+        return t
+
+    def slab_batch(self, reduce):
+        """a GuardedSlabs for the `slabs=` of a weight-gradient call: its slabs are checked with the launch's other outputs"""
+        self.slabs.append(GuardedSlabs(self.dev, reduce, self.KFLAT))
+        return self.slabs[-1]
+
+    def ref(self, what, got, want, tol, scale=None):
+        """got (a device tensor or a callable evaluated after the launches) against `want`: rel_err < tol, or bitwise when tol == 0
+        (scale: the error's denominator where a test states another one than max |want|)"""
+        self.refs.append((what, got, want, tol, scale))
+
+    def check(self):
+        self.check_guards()                                                                      # 3
+        for name, (view, _) in list(self.outs.items()) + list(self.flats.items()):                # 4
+            assert bool(torch.isfinite(view).all()), "%s (pad %d): not finite" % (name, self.pad)
+        for name, t in self.parts.items():
+            assert bool(torch.isfinite(t).all()), "partials %s (pad %d): not finite" % (name, self.pad)
+        for s in self.slabs:
+            s.check_finite("slabs (pad %d)" % self.pad)
+        for what, got, want, tol, scale in self.refs:                                            # 1
+            got = got() if callable(got) else got
+            want = want() if callable(want) else want
+            if tol == 0:
+                assert torch.equal(got.cpu(), want.cpu()), "%s (pad %d): not bitwise equal" % (what, self.pad)
+            else:
+                e = rel_err(got.cpu(), want.cpu()) if scale is None else (got.cpu().double() - want.cpu().double()).abs().max().item() / scale
+                print("%s (pad %d): %.2e" % (what, self.pad, e))
+                assert e < tol, "%s (pad %d): %.3e >= %.1e" % (what, self.pad, e, tol)
+
+    def check_guards(self):
+        for name, (view, whole) in self.outs.items():
+            assert_guards_untouched(whole, view.shape, SENTINEL, self.FRONT, self.BACK, "%s (pad %d)" % (name, self.pad))
+        for name, (view, whole) in self.masks.items():
+            assert_guards_untouched(whole, view.shape, MASK_FILL, self.FRONT, self.BACK, "mask %s (pad %d)" % (name, self.pad))
+        for name, (view, whole) in self.flats.items():
+            assert_flat_guards_untouched(whole, view.numel(), SENTINEL, self.KFLAT, "%s (pad %d)" % (name, self.pad))
+        for s in self.slabs:
+            s.check_guards("slabs (pad %d)" % self.pad)
+
+    def check_nothing_written(self):
+        """5: a rejected call launched nothing"""
+        for name, (_, whole) in list(self.outs.items()) + list(self.flats.items()):
+            assert bool((whole == SENTINEL).all()), "%s (pad %d): written by a rejected call" % (name, self.pad)
+        for s in self.slabs:
+            s.check_nothing_written("slabs (pad %d)" % self.pad)
+
+
+def drive(dev, fn, pad, bitwise=True, launch=Launch):
+    """run `fn` tight and with `pad`, apply the five assertions"""
+    tight, padded = launch(dev, 0), launch(dev, pad)
+    fn(tight)
+    fn(padded)
+    torch.cuda.synchronize()
+    tight.check()
+    padded.check()
+    # (a variant that a padded ld is rejected for has an output in the tight launch only)
+    assert set(tight.outs) >= set(padded.outs) and set(tight.flats) == set(padded.flats) and set(tight.masks) >= set(padded.masks)
+    if bitwise:                                                                                  # 2
+        for kind in ("outs", "flats", "masks"):
+            for name, (view, _) in getattr(padded, kind).items():
+                assert torch.equal(view, getattr(tight, kind)[name][0]), "%s: pad %d differs from the tight launch" % (name, pad)
+    return tight, padded
+
+
+def rejected(dev, fn, pad, launch=Launch):
+    """the ABI does not take this leading dimension: the call raises and writes nothing"""
+    import pytest
+    from sar_amd import _lib as L
+    g = launch(dev, pad)
+    with pytest.raises((L.SarError, AssertionError)):
+        fn(g)
+    torch.cuda.synchronize()
+    g.check_nothing_written()
+
+
+class GuardedSlabs:
+    """What a weight-gradient call takes as `slabs=` (duck-typed to sar_amd.ops.SlabBatch: slab() and add()), with every slab a view
+    into a guarded flat range: the live nsplit * n elements start as NaN -- an element no workgroup writes reaches the reduced
+    gradient as NaN --, the KFLAT elements on either side hold the output sentinel.  add() reduces at once by `reduce(slab, nsplit,
+    n, out)` (on the GPU: sar_slab_reduce_f32, the launch ops issues behind a weight gradient without a batch)."""
+
+    def __init__(self, dev, reduce, k=8):
+        self.dev, self.reduce, self.k, self.items = dev, reduce, k, []
+
+    def slab(self, out, nsplit, n):
+        view, whole = guarded_flat(nsplit * n, SENTINEL, self.dev, self.k)
+        view.fill_(NAN)
+        self.items.append((view, whole, nsplit, n))
+        return view.view(nsplit, n)
+
+    def add(self, slab, nsplit, n, out):
+        assert any(slab.data_ptr() == v.data_ptr() and (nsplit, n) == (ns, nn) for v, _, ns, nn in self.items), "not a slab of this batch"
+        self.reduce(slab, nsplit, n, out)
+
+    def check_guards(self, what=""):
+        for view, whole, nsplit, n in self.items:
+            assert_flat_guards_untouched(whole, nsplit * n, SENTINEL, self.k, "%s: (%d, %d) slab" % (what, nsplit, n))
+
+    def check_finite(self, what=""):
+        assert self.items, "%s: the call asked for no slab" % what
+        for view, _, nsplit, n in self.items:
+            bad = ~torch.isfinite(view)
+            if bool(bad.any()):
+                i = int(bad.nonzero()[0])
+                raise AssertionError("%s: element %d of slab %d of a (%d, %d) slab buffer was never written or is not finite (%d in all)"
+                                     % (what, i % n, i // n, nsplit, n, int(bad.sum())))
+
+    def check_nothing_written(self, what=""):
+        for view, whole, nsplit, n in self.items:
+            self.check_guards(what)
+            assert bool(torch.isnan(view).all()), "%s: written by a rejected call" % what
+
+
 # ---- guard bands of the bf16 (CN8) kernels: planes of 16-byte units (include/sar_hip.h "CN8"; tests/test_gpu_cn8_guard_bands.py)
 
 def cn8_units(src):
