@@ -13,7 +13,7 @@ from . import profiler
 from ._lib import ConvDesc, WgradDesc, check, ptr, stream_ptr
 
 
-_PROFILE_SHAPES = __import__("os").environ.get("SAR_PROFILE_SHAPES", "0") == "1"
+_PROFILE_SHAPES = os.environ.get("SAR_PROFILE_SHAPES", "0") == "1"
 
 
 def _f32(t):
@@ -144,11 +144,10 @@ def shared_side_stream(device, priority=0):
             st = torch.cuda.Stream(device=device, priority=int(priority))
         else:
             # a stream that leaves some CUs to the main chain (sar_stream_create_cu_mask), wrapped for torch's stream API
-            import ctypes as _C
-            words = (_C.c_uint32 * len(mask))(*mask)
-            h = _C.c_void_p()
+            words = (C.c_uint32 * len(mask))(*mask)
+            h = C.c_void_p()
             with torch.cuda.device(device):
-                check(L.load().sar_stream_create_cu_mask(words, len(mask), _C.byref(h)), "sar_stream_create_cu_mask")
+                check(L.load().sar_stream_create_cu_mask(words, len(mask), C.byref(h)), "sar_stream_create_cu_mask")
             st = torch.cuda.ExternalStream(h.value, device=device)
         _side_streams[key] = st
     return st
@@ -218,7 +217,7 @@ def affine_bound(scale, shift, src_cell, cell):
 DEFAULT_SPLIT = None
 
 
-TAP1_SPLIT = __import__("os").environ.get("SAR_TAP1_SPLIT", "1") == "1"      # the 1-tap temporal operator on conv_tap1_split_kernel (A/B switch)
+TAP1_SPLIT = os.environ.get("SAR_TAP1_SPLIT", "1") == "1"      # the 1-tap temporal operator on conv_tap1_split_kernel (A/B switch)
 
 
 def split_applicable(mode, V, Kc, M, taps, stride, tables=None, pro=None, transposed=False, pad=0):
@@ -337,19 +336,19 @@ def conv_gemm(mode, src, out, W, w_stride_tap, w_stride_c, *, B, V, T_src, T_out
     return (partials, nparts) if partials is not None else None
 
 
-_WGRAD1_SLOTS = int(__import__("os").environ.get("SAR_WGRAD1_SLOTS", "1024"))      # workgroups in flight of the 1-tap weight gradients
-_WGRAD9_SLOTS = int(__import__("os").environ.get("SAR_WGRAD9_SLOTS", "1024"))      # ... of the 9-tap temporal ones (sweep knobs)
-_WGRADG_SLOTS = int(__import__("os").environ.get("SAR_WGRADG_SLOTS", "512"))       # ... of the graph ones
+_WGRAD1_SLOTS = int(os.environ.get("SAR_WGRAD1_SLOTS", "1024"))      # workgroups in flight of the 1-tap weight gradients
+_WGRAD9_SLOTS = int(os.environ.get("SAR_WGRAD9_SLOTS", "1024"))      # ... of the 9-tap temporal ones (sweep knobs)
+_WGRADG_SLOTS = int(os.environ.get("SAR_WGRADG_SLOTS", "512"))       # ... of the graph ones
 
 
 # columns per workgroup of the first layer's streaming weight gradient (graph_wgrad_small4_kernel: 256-column iterations)
-_WGRAD_SMALL_COLS = int(__import__("os").environ.get("SAR_WGRAD_SMALL_COLS", "4096"))
+_WGRAD_SMALL_COLS = int(os.environ.get("SAR_WGRAD_SMALL_COLS", "4096"))
 
 # SAR_SLAB_BATCH=0: every weight gradient reduces its slabs by its own launch again (A/B switch)
-SLAB_BATCH = __import__("os").environ.get("SAR_SLAB_BATCH", "1") == "1"
+SLAB_BATCH = os.environ.get("SAR_SLAB_BATCH", "1") == "1"
 # when an engine flushes its batch: "end" = at the end of backward (and before a bucket goes to the all-reduce), "bucket" = at every
 # bucket boundary also without a data-parallel callback, "block" = behind every block
-SLAB_FLUSH = __import__("os").environ.get("SAR_SLAB_FLUSH", "end")
+SLAB_FLUSH = os.environ.get("SAR_SLAB_FLUSH", "end")
 
 
 class SlabBatch:
@@ -523,7 +522,7 @@ def data_bn_bwd_reduce(x, bone_parent, dy, mean, partials, motion=False):
                                               ptr(partials), stream_ptr()), "sar_data_bn_bwd_reduce_f32")
 
 
-RELU_MASK = __import__("os").environ.get("SAR_RELU_MASK", "1") == "1"   # block tails write / read a 1-bit ReLU mask (A/B switch)
+RELU_MASK = os.environ.get("SAR_RELU_MASK", "1") == "1"   # block tails write / read a 1-bit ReLU mask (A/B switch)
 
 
 def relu_mask(u):
@@ -554,14 +553,14 @@ def bn_add_relu_fwd(u, sc, sh, res_kind, r, rsc, rsh, y, mask=None, amax_cell=No
                                            u.shape[0], u.shape[1], u.stride(0), stream_ptr()), "sar_bn_add_relu_fwd_f32")
 
 
-_REDUCE_CHUNK = int(__import__("os").environ.get("SAR_BWD_REDUCE_CHUNK", "8192"))      # row elements per workgroup of the BN-backward reductions
+_REDUCE_CHUNK = int(os.environ.get("SAR_BWD_REDUCE_CHUNK", "8192"))      # row elements per workgroup of the BN-backward reductions
 
 
 # SAR_BN_TAIL=1: the BatchNorm-backward finalisation of every block tail runs in the reduce kernel's last workgroup instead of in
 # its own launch(es).  Measured (three interleaved rounds each): fp32 59.44 vs 59.49 ms, bf16 13.37 vs 13.32, Path B 6.35 vs 6.37
 # -- the launches it removes were waiting beside useful work of the other stream, not in front of it.  OFF by default: the sc1
 # hand-off it relies on is measured behaviour of this part (MI355X_MICROARCH.md), not an architectural guarantee, and buys nothing.
-BN_TAIL = __import__("os").environ.get("SAR_BN_TAIL", "0") == "1"
+BN_TAIL = os.environ.get("SAR_BN_TAIL", "0") == "1"
 _tickets = {}
 
 
@@ -1055,7 +1054,7 @@ def conv2d_gemm(src, out, W, w_stride_tap, w_stride_c, *, epi=L.SAR_EPI_NONE, au
     return (partials, nparts) if partials is not None else None
 
 
-_C2D_WG_SLOTS = int(__import__("os").environ.get("SAR_C2D_WG_SLOTS", "512"))
+_C2D_WG_SLOTS = int(os.environ.get("SAR_C2D_WG_SLOTS", "512"))
 
 
 def conv2d_wgrad(src, dout, dW_tcm, *, split="default", bounds=None, slabs=None, **geo):

@@ -9,14 +9,20 @@ view -- so the forward reads the master weights and the weight-gradient kernels 
 only the (tap, m, c) layout of the data-gradient GEMMs is re-packed, once per step on the side stream.  Activations are CN matrices [C][B*H*W]; per BasicBlock the tensors crossing a BatchNorm barrier
 (c1, c2, downsample out, block out) are materialised once; BN+ReLU is folded into the consumer conv's operand load,
 BN statistics into the producer's epilogue, the block tail reuses the ST-GCN BN+add+ReLU kernels.
+
+The flat storage, the weight-gradient stream (_on_side), the third stream (_fork / _join) and the hand-over of the gradient
+buckets are sar_amd/engine.py's, shared with the ST-GCN family; this module declares the parameters, keeps its permuted _view and
+says WHAT runs beside the main chain (DS_STREAM below) and which block completes a bucket (_make_buckets).
 """
 import math
+import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import ops
+from .engine import FlatEngine
 from .stgcn import _BN, SPLIT_ARITH
 
 BN_EPS = 1e-5            # torch BatchNorm2d defaults (models/resnet18.py norm_layer = nn.BatchNorm2d)
@@ -25,8 +31,8 @@ LAYERS = [2, 2, 2, 2]    # models/resnet18.py:274
 # arithmetic of an engine built without an explicit `mfma` (the parity suites run once per value, tests/conftest.py):
 # "fp32" = fp32 MFMA kernels; "f32_split" / "f32_split_bf16x6" = fp32 results on the fp16 / bf16 matrix pipe for the 3x3 / stride-1
 # convolutions (csrc/conv2d_split.hip), everything else unchanged
-DEFAULT_MFMA = __import__("os").environ.get("SAR_MFMA_PATHB", "fp32")
-_SPLIT_KINDS = set(__import__("os").environ.get("SAR_SPLIT_KINDS_PATHB", "fwd,dgrad,wgrad").split(","))
+DEFAULT_MFMA = os.environ.get("SAR_MFMA_PATHB", "fp32")
+_SPLIT_KINDS = set(os.environ.get("SAR_SPLIT_KINDS_PATHB", "fwd,dgrad,wgrad").split(","))
 
 
 class _Conv:
@@ -35,7 +41,7 @@ class _Conv:
         self.taps = k * k
 
 
-SLAB_BATCH_PATHB = __import__("os").environ.get("SAR_SLAB_BATCH_PATHB", "0") == "1"
+SLAB_BATCH_PATHB = os.environ.get("SAR_SLAB_BATCH_PATHB", "0") == "1"
 # Fork / join of what does not depend on the main chain (round 6; SAR_PATHB_DS_STREAM=0: everything on the main stream again).  At bs = 32
 # a step is a serial chain of ~150 launches of 4-50 us: the down-sampling branch of the three stride-2 blocks (1x1 convolution + its
 # BatchNorm finalisation forward; its backward finalisation and the dense 1x1 product of its data gradient backward), the nine Samuelson
@@ -43,15 +49,17 @@ SLAB_BATCH_PATHB = __import__("os").environ.get("SAR_SLAB_BATCH_PATHB", "0") == 
 # stream and are joined where their results are needed.  Same launches, same order per tensor: bit-identical
 # (tests/test_gpu_slab_batch.py); interleaved processes (tools/ab_pathb2.sh, profiles/r06_pathB_fork_ab.txt): fp32 4 976 -> 5 222 clips/s
 # (+4.9 %), f32_split 7 098 -> 7 386 (+4.1 %)
-DS_STREAM = __import__("os").environ.get("SAR_PATHB_DS_STREAM", "1") == "1"
+DS_STREAM = os.environ.get("SAR_PATHB_DS_STREAM", "1") == "1"
 # The BatchNorm-backward finalisation of a block tail (bn2 and the down-sampling BN) in the reduce kernel's last workgroup per channel
 # (ops.BN_TAIL) instead of one or two launches behind it.  One bench.py process per entry (profiles/r06_pathB_fork_ab.txt):
 # fp32 5 214 -> 5 220 clips/s (neutral), f32_split 7 208 -> 7 330 (+1.7 %): on for the split arithmetic ("split"; "1" / "0": always / never;
 # SAR_BN_TAIL=1 still turns it on everywhere)
-BN_TAIL_PATHB = __import__("os").environ.get("SAR_BN_TAIL_PATHB", "split")
+BN_TAIL_PATHB = os.environ.get("SAR_BN_TAIL_PATHB", "split")
 
 
-class ResNet18:
+class ResNet18(FlatEngine):
+    moving_suffixes = (".running_mean", ".running_var")
+
     def __init__(self, num_classes=60, num_filters=64, device="cuda", seed=0, mfma=None):
         L.load()
         self.device = torch.device(device)
@@ -59,6 +67,19 @@ class ResNet18:
         assert self.mfma == "fp32" or self.mfma in SPLIT_ARITH, self.mfma
         self.split = SPLIT_ARITH.get(self.mfma)
         self.num_classes, self.nf = num_classes, num_filters
+        # the constructor's steps, as in sar_amd/stgcn.py
+        self._declare_params()
+        total = self._allocate_flat(("adam_m", "adam_v"), ("step_dev",))
+        self.bn = {name: _BN(c, self.device) for name, c in self.bn_names}
+        self._init_params(seed)
+        self._init_device()
+        self._init_operand_images()
+        self._buckets = self._make_buckets(total)
+
+    # ------------------------------------------------------------------ the constructor's steps
+    def _declare_params(self):
+        """the parameter table (the reference's state_dict names, torch shapes), in the order of the flat buffer; self.blocks:
+        (name prefix, channels in, channels out, stride, has a down-sampling branch)"""
         self.shapes, self.convs, self.bn_names, self.blocks = {}, {}, [], []
 
         def conv(name, cin, cout, k, stride):
@@ -70,11 +91,11 @@ class ResNet18:
             self.shapes[name + ".bias"] = (c,)
             self.bn_names.append((name, c))
 
-        conv("conv1", 1, num_filters, 7, 2)
-        bn("bn1", num_filters)
-        inpl = num_filters
+        conv("conv1", 1, self.nf, 7, 2)
+        bn("bn1", self.nf)
+        inpl = self.nf
         for li, nb in enumerate(LAYERS):
-            planes = num_filters * 2 ** li
+            planes = self.nf * 2 ** li
             for bi in range(nb):
                 pre = "layer%d.%d." % (li + 1, bi)
                 stride = 2 if (li > 0 and bi == 0) else 1
@@ -89,37 +110,27 @@ class ResNet18:
                 self.blocks.append((pre, inpl, planes, stride, ds))
                 inpl = planes
         self.c_last = inpl
-        self.shapes["fc.weight"] = (num_classes, inpl)
-        self.shapes["fc.bias"] = (num_classes,)
-        total, self.offsets = 0, {}
-        for k, shp in self.shapes.items():
-            self.offsets[k] = total
-            total += (int(np.prod(shp)) + 3) // 4 * 4
-        self.n_params = sum(int(np.prod(s)) for s in self.shapes.values())
+        self.shapes["fc.weight"] = (self.num_classes, inpl)
+        self.shapes["fc.bias"] = (self.num_classes,)
+
+    def _init_device(self):
+        """streams and per-step state"""
         dev = self.device
-        z = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
-        self.flat, self.grad, self.adam_m, self.adam_v = z(total), z(total), z(total), z(total)
-        self.lr_dev, self.step_dev = z(1), z(1)
-        self.p = {k: self._view(self.flat, k) for k in self.shapes}
-        self.g = {k: self._view(self.grad, k) for k in self.shapes}
-        self.bn = {name: _BN(c, dev) for name, c in self.bn_names}
-        self._init_params(seed)
-        self._saved = None
-        # weight-gradient kernels feed only the optimizer: second stream, as in sar_amd/stgcn.py (SAR_WGRAD_STREAM=0: off)
-        import os
-        self._side = (ops.shared_side_stream(dev) if dev.type == "cuda" and os.environ.get("SAR_WGRAD_STREAM", "1") == "1"
-                      else None)
-        # one slab reduction per gradient bucket (ops.SlabBatch) -- OFF here: at bs = 32 the per-gradient reductions hide beside the
+        # weight-gradient kernels feed only the optimizer: second stream, as in sar_amd/stgcn.py (SAR_WGRAD_STREAM=0: off).
+        # One slab reduction per gradient bucket (ops.SlabBatch) -- OFF here: at bs = 32 the per-gradient reductions hide beside the
         # main chain, a batched one lands on the tail of backward (interleaved, profiles/r06_slab_batch_ab.txt: 4.62 -> 4.74 ms in
         # the split arithmetic, 6.40 -> 6.44 / 6.33 at the end / per stage in fp32); SAR_SLAB_BATCH_PATHB=1 turns it on
-        self._slabs = ops.SlabBatch() if (ops.SLAB_BATCH and SLAB_BATCH_PATHB) else None
-        self._slab_flush = ops.SLAB_FLUSH
-        self._aux = ops.shared_aux_stream(dev) if (DS_STREAM and dev.type == "cuda") else None
-        self._bounds_forked = False
-        self._prepacked = None
+        self._init_streams(0 if os.environ.get("SAR_WGRAD_STREAM", "1") == "1" else None, ops.SLAB_BATCH and SLAB_BATCH_PATHB, DS_STREAM)
+        self._saved = self._prepacked = self._wb_ready = None
+        self._fc_forked = False
         # side streams of the launches that fan out (stride-2 data gradients): owned by this engine, not by the library
-        with torch.cuda.device(dev):
-            self._ctx = L.Context() if dev.type == "cuda" else None
+        self._ctx = None
+        if dev.type == "cuda":
+            with torch.cuda.device(dev):
+                self._ctx = L.Context()
+
+    def _init_operand_images(self):
+        dev = self.device
         # The data-gradient GEMMs read (tap, m, c): ONE re-layout launch per training step, on the side stream (the forward
         # reads the stored (tap, c, m) weights in place and the weight-gradient kernels write self.grad in place).
         self._woff, off = {}, 0
@@ -133,7 +144,7 @@ class ResNet18:
             off += (n + 3) // 4 * 4
         pb.finalize(dev)
         self._perm_bwd = pb
-        self._wb = z(off)
+        self._wb = torch.zeros(off, dtype=torch.float32, device=dev)
         # Split arithmetic: the term images of every 3x3 / stride-1 weight tensor -- forward view (tap, c, m) and data-gradient view
         # (mirrored taps, c and m exchanged: include/sar_hip.h sar_conv2d_gemm_split) -- written by ONE launch per step from the
         # master weights, and the bound cells of the source operands (zeroed once per step; raised by the producing passes)
@@ -155,20 +166,22 @@ class ResNet18:
             sp.finalize(dev)
             self.spacked = sp
             self._cells = torch.zeros(max(1, len(self._cell_of)), dtype=torch.int32, device=dev)
-        # Gradient buckets for the data-parallel exchange (main_spectrogram.py:118-119), in the order backward() completes
-        # them: [layer4 + fc], [layer3], [layer2], [conv1 + bn1 + layer1].  Each is a contiguous slice of the flat gradient
-        # buffer (parameters are laid out in declaration order), so that a bucket can be all-reduced while the earlier layers are
-        # still in backward.
-        names = list(self.shapes)
-        stage_of = lambda k: (4 if k.startswith(("layer4.", "fc.")) else 3 if k.startswith("layer3.") else
-                              2 if k.startswith("layer2.") else 1)
-        self._buckets = []
-        for st in (4, 3, 2, 1):
-            ks = [k for k in names if stage_of(k) == st]
-            lo = min(self.offsets[k] for k in ks)
-            hi = max(self.offsets[k] + (int(np.prod(self.shapes[k])) + 3) // 4 * 4 for k in ks)
-            self._buckets.append(dict(stage=st, lo=lo, hi=hi))
-        assert sorted((b["lo"], b["hi"]) for b in self._buckets)[0][0] == 0 and max(b["hi"] for b in self._buckets) == total
+
+    def _make_buckets(self, total):
+        """Gradient buckets for the data-parallel exchange (main_spectrogram.py:118-119), in the order backward() completes them:
+        [layer4 + fc], [layer3], [layer2], [conv1 + bn1 + layer1] -- a stage is complete behind its first (stride-2) block.  Each is
+        a contiguous slice of the flat gradient buffer (parameters are laid out in declaration order), so that a bucket can be
+        all-reduced while the earlier layers are still in backward.  Entries as FlatEngine._buckets."""
+        out, hi = [], total
+        for i in reversed(range(1, len(self.blocks))):
+            pre, _, _, stride, _ = self.blocks[i]
+            if stride != 1:
+                lo = self.offsets[pre + "conv1.weight"]
+                out.append((i, lo, hi))
+                hi = lo
+        out.append((-1, 0, hi))
+        assert sum(h - l for _, l, h in out) == total
+        return out
 
     def _view(self, flat, name):
         """The named tensor in torch's shape.  Conv weights are STORED in the forward GEMM's operand order (kh, kw, c, m)
@@ -202,20 +215,7 @@ class ResNet18:
 
     def load_params(self, params):
         self._prepacked = None           # images issued by prepack() would be those of the old weights
-        for k, v in params.items():
-            if k in self.p:
-                self.p[k].copy_(v.to(torch.float32).reshape(self.shapes[k]))
-            elif k.endswith(".running_mean"):
-                self.bn[k[:-13]].moving_mean.copy_(v.to(torch.float32))
-            elif k.endswith(".running_var"):
-                self.bn[k[:-12]].moving_var.copy_(v.to(torch.float32))
-
-    def state_dict(self):
-        out = {k: v.detach().cpu().clone() for k, v in self.p.items()}
-        for k, b in self.bn.items():
-            out[k + ".running_mean"] = b.moving_mean.cpu().clone()
-            out[k + ".running_var"] = b.moving_var.cpu().clone()
-        return out
+        super().load_params(params)
 
     # ------------------------------------------------------------------ weights
     def _pack(self, need_bwd):
@@ -224,13 +224,8 @@ class ResNet18:
             self.spacked.refresh(self.flat)
             self._cells.zero_()
         if need_bwd:            # only the backward pass reads the data-gradient layouts: off the forward's critical path
-            if self._side is None:
-                self._perm_bwd.run(self.flat, self._wb)
-            else:
-                main = torch.cuda.current_stream()
-                self._side.wait_stream(main)                  # after the optimizer step that produced self.flat
-                with torch.cuda.stream(self._side):
-                    self._perm_bwd.run(self.flat, self._wb)
+            self._on_side(lambda: self._perm_bwd.run(self.flat, self._wb))      # after the optimizer step that produced self.flat
+            if self._side is not None:
                 self._wb_ready = torch.cuda.Event()
                 self._wb_ready.record(self._side)
 
@@ -240,9 +235,7 @@ class ResNet18:
         does not read the resnet's weights (sar_amd/train.py).  forward() then joins instead of packing.  No-op without the stream."""
         if self._aux is None or self._prepacked is not None:
             return
-        self._aux.wait_stream(torch.cuda.current_stream())      # behind the optimizer step that produced self.flat
-        with torch.cuda.stream(self._aux):
-            self._pack(training)
+        self._fork(lambda: self._pack(training))      # behind the optimizer step that produced self.flat
         self._prepacked = bool(training)
 
     def _w(self, name, bwd=False):
@@ -329,11 +322,9 @@ class ResNet18:
         self._bounds_forked = False
         if training and self._aux is not None and self._cells is not None:
             # every Samuelson bound of the step (they depend on gamma / beta and the sample counts only) on the third stream, beside
-            # the stem: nine 4-us launches off the serial chain; joined in front of the first block
-            if not join_aux:
-                self._aux.wait_stream(torch.cuda.current_stream())  # behind the zeroing of the cells (prepacked: zeroed on that stream)
-            with torch.cuda.stream(self._aux):
-                self._all_bn_bounds(B, H, W)
+            # the stem: nine 4-us launches off the serial chain; joined in front of the first block.  Behind the zeroing of the cells:
+            # prepacked, they were zeroed on that stream
+            self._fork(lambda: self._all_bn_bounds(B, H, W), after="nothing" if join_aux else "main")
             self._bounds_forked = join_aux = True
         X0 = x.view(1, B * H * W)
         c0, r, H1, W1 = self._conv_fwd("conv1", X0, B, H, W, training)
@@ -346,34 +337,33 @@ class ResNet18:
         saved = dict(x0=X0, c0=c0, B=B, H=H, W=W, H1=H1, W1=W1, H2=H2, W2=W2, blocks=[])
         Hc, Wc = H2, W2
         if join_aux:
-            torch.cuda.current_stream().wait_stream(self._aux)
+            self._join()
         if self._bounds_forked:
             pass
         elif training and self._cell(self.blocks[0][0] + "conv1", "f") is not None:
             # the stem tail is max-pool(relu(bn1(c0))): bounded by bn1's Samuelson bound
             ops.bn_bound(self.p["bn1.weight"], self.p["bn1.bias"], B * H1 * W1, self._cell(self.blocks[0][0] + "conv1", "f"))
         for bi_, (pre, inpl, planes, stride, ds) in enumerate(self.blocks):
-            dsc = bd = None
+            dsc, bd = None, self.bn.get(pre + "downsample.1")
             forked = ds and self._aux is not None
+            def branch(out=None):
+                out, rd, _, _ = self._conv_fwd(pre + "downsample.0", h, B, Hc, Wc, training, out=out)
+                self._bn_stats(pre + "downsample.1", rd, out.shape[1], training)
+                return out
             if forked:       # the down-sampling branch on the third stream; its output lives in main-stream memory
                 cd = self.convs[pre + "downsample.0"]
                 Hd, Wd = (Hc + 2 * cd.pad - cd.k) // cd.stride + 1, (Wc + 2 * cd.pad - cd.k) // cd.stride + 1
                 dsc = torch.empty((cd.cout, B * Hd * Wd), dtype=torch.float32, device=dev)
-                self._aux.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(self._aux):
-                    _, rd, _, _ = self._conv_fwd(pre + "downsample.0", h, B, Hc, Wc, training, out=dsc)
-                    bd = self._bn_stats(pre + "downsample.1", rd, B * Hd * Wd, training)
-                h.record_stream(self._aux)
+                self._fork(lambda: branch(dsc), h)
             c1, r1, Ho, Wo = self._conv_fwd(pre + "conv1", h, B, Hc, Wc, training)
             b1 = self._bn_stats(pre + "bn1", r1, B * Ho * Wo, training)
             c2, r2, _, _ = self._conv_fwd(pre + "conv2", c1, B, Ho, Wo, training, pro=(b1.scale, b1.shift),
                                           bn_src=(pre + "bn1", B * Ho * Wo))
             b2 = self._bn_stats(pre + "bn2", r2, B * Ho * Wo, training)
-            if ds and not forked:
-                dsc, rd, _, _ = self._conv_fwd(pre + "downsample.0", h, B, Hc, Wc, training)
-                bd = self._bn_stats(pre + "downsample.1", rd, B * Ho * Wo, training)
             if forked:
-                torch.cuda.current_stream().wait_stream(self._aux)
+                self._join()
+            elif ds:
+                dsc = branch()
             y = torch.empty_like(c2)
             ymask = ops.relu_mask(y) if training else None  # 1 bit per element: what the BatchNorm-backward passes read instead of y
             nxt = self.blocks[bi_ + 1][0] + "conv1" if bi_ + 1 < len(self.blocks) else None
@@ -407,25 +397,7 @@ class ResNet18:
         def run():
             ops.conv2d_wgrad(X, dout, self.grad[o:o + n], B=B, Kc=cv.cin, M=cv.cout, H_src=H, W_src=W, H_out=Ho, W_out=Wo, KH=cv.k,
                              KW=cv.k, stride=cv.stride, pad=cv.pad, pro=pro, pro_relu=pro is not None, slabs=self._slabs, **sa)
-        if self._side is None:
-            run()
-        else:       # ordered after everything issued so far; X / dout must outlive the side stream's use
-            self._side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._side):
-                run()
-            X.record_stream(self._side)
-            dout.record_stream(self._side)
-
-    def _flush_slabs(self):
-        """the slabs of every weight gradient issued since the last flush are summed by ONE launch on the weight-gradient stream
-        (ops.SlabBatch): before a bucket is handed to the all-reduce and at the end of backward()"""
-        if self._slabs is None:
-            return
-        if self._side is None:
-            self._slabs.flush()
-        else:
-            with torch.cuda.stream(self._side):
-                self._slabs.flush()
+        self._on_side(run, X, dout)
 
     def _conv_dgrad(self, name, dout, B, H, W, Ho, Wo, **epi):
         """gradient w.r.t. the conv's input (H, W) from dout at (Ho, Wo)."""
@@ -443,30 +415,14 @@ class ResNet18:
                             b.k1, b.k2, b.k3)
         return b
 
-    def _bucket_done(self, bi, cb):
-        """Every gradient of bucket bi has been ISSUED: its weight gradients on the side stream, its BatchNorm / fc gradients
-        on the main stream.  cb(bi, flat slice, events) may start the
-        slice's all-reduce as soon as the events have completed -- the main stream goes on with the earlier layers."""
-        bk = self._buckets[bi]
-        events = []
-        self._flush_slabs()
-        if self._side is not None:
-            ev = torch.cuda.Event()
-            ev.record(self._side)
-            events.append(ev)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        events.append(ev)
-        cb(bi, self.grad[bk["lo"]:bk["hi"]], events)
-
     def backward(self, dlogits, need_dx=False, bucket_cb=None):
         """Gradients of every parameter into self.g; need_dx additionally returns d loss / d image (B,1,H,W) -- only
-        wanted when the image depends on trainable VirtualRadar parameters.  bucket_cb: see _bucket_done (data-parallel
+        wanted when the image depends on trainable VirtualRadar parameters.  bucket_cb: see FlatEngine._bucket_done (data-parallel
         training: the gradient exchange overlaps the rest of backward)."""
         sv = self._saved
         assert sv is not None
         dev, B = dlogits.device, sv["B"]
-        if self._side is not None and getattr(self, "_wb_ready", None) is not None:
+        if self._side is not None and self._wb_ready is not None:
             torch.cuda.current_stream().wait_event(self._wb_ready)      # the data-gradient weight layouts (packed on the side stream)
             self._wb_ready = None
         dwt = torch.empty_like(sv["wt"])
@@ -475,12 +431,10 @@ class ResNet18:
         if self._aux is not None and bucket_cb is None:
             # the classifier's parameter gradients feed nothing but the optimizer: beside the chain (joined at the end of backward);
             # under data parallelism they belong to the first bucket, whose events are recorded on the main stream: serial there
-            self._aux.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._aux):
+            def fc_params():
                 ops.fc_bwd(sv["feat"], sv["wt"], dlogits, dwt, self.g["fc.bias"], None)
                 ops.transpose(dwt, self.g["fc.weight"], 1, self.c_last, self.num_classes)
-            dwt.record_stream(self._aux)
-            dlogits.record_stream(self._aux)
+            self._fork(fc_params, dwt, dlogits)
             ops.fc_bwd(sv["feat"], sv["wt"], dlogits, None, None, dfeat)
             self._fc_forked = True
         else:
@@ -488,8 +442,8 @@ class ResNet18:
             ops.transpose(dwt, self.g["fc.weight"], 1, self.c_last, self.num_classes)
         dY = torch.empty((self.c_last, B * sv["Hl"] * sv["Wl"]), dtype=torch.float32, device=dev)
         ops.pool_bwd(dfeat, B, sv["Hl"] * sv["Wl"], 1, dY)
-        nblk = len(self.blocks)
-        for bidx, ((pre, inpl, planes, stride, ds), sb) in enumerate(zip(reversed(self.blocks), reversed(sv["blocks"]))):
+        for bidx in reversed(range(len(self.blocks))):
+            (pre, inpl, planes, stride, ds), sb = self.blocks[bidx], sv["blocks"][bidx]
             X, c1, c2, dsc, y = sb["X"], sb["c1"], sb["c2"], sb["dsc"], sb["y"]
             H, W, Ho, Wo = sb["H"], sb["W"], sb["Ho"], sb["Wo"]
             n_out = B * Ho * Wo
@@ -503,20 +457,26 @@ class ResNet18:
                 ops.bn_add_relu_bwd_reduce(dY, y, c2, dsc, b2.mean, bd.mean if ds else None, tail=tail)
             else:
                 part, nparts = ops.bn_add_relu_bwd_reduce(dY, y, c2, dsc, b2.mean, bd.mean if ds else None, mask=sb.get("ymask"))
+                fin_ds = lambda: self._bn_bwd(pre + "downsample.1", part, nparts, nparts * 4, 4, 2, n_out)
                 if ds and self._aux is not None:     # the two finalisations read the same partial sums: side by side
-                    self._aux.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(self._aux):
-                        self._bn_bwd(pre + "downsample.1", part, nparts, nparts * 4, 4, 2, n_out)
-                    part.record_stream(self._aux)
+                    self._fork(fin_ds, part)
                 self._bn_bwd(pre + "bn2", part, nparts, nparts * 4, 4, 1, n_out)
                 if ds and self._aux is not None:
-                    torch.cuda.current_stream().wait_stream(self._aux)
+                    self._join()
                 elif ds:
-                    self._bn_bwd(pre + "downsample.1", part, nparts, nparts * 4, 4, 2, n_out)
+                    fin_ds()
             dc2 = torch.empty_like(c2)
             ddsc = torch.empty_like(dsc) if ds else None
             ops.bn_add_relu_bwd_apply(dY, y, c2, dsc, (b2.k1, b2.k2, b2.k3), rk, dc2, ddsc, None if ds else dY, mask=sb.get("ymask"),
                                       amax_cell=self._cell(pre + "conv2", "b"))      # bound of dc2 for conv2's split data gradient
+            # the 1x1 / stride 2 data gradient is non-zero at the even pixels only: computed at the small resolution (a plain stride-1
+            # product) and added there by the parity-class launches of conv1's data gradient.  Its output is allocated HERE, in front
+            # of the event its fork waits for: the third stream may write it before the main stream's later launches have run, so the
+            # block must not be one that those launches' temporaries have just handed back to the allocator
+            cd = self.convs.get(pre + "downsample.0")
+            even = ds and cd.k == 1 and cd.stride == 2 and cd.pad == 0 and stride == 2 and H == 2 * Ho and W == 2 * Wo
+            aux = torch.empty((cd.cin, n_out), dtype=torch.float32, device=dev) if even else dY
+            ddsc_ready = None
             if ds and self._aux is not None:
                 ddsc_ready = torch.cuda.Event()
                 ddsc_ready.record(torch.cuda.current_stream())
@@ -527,32 +487,19 @@ class ResNet18:
             self._bn_bwd(pre + "bn1", pm[0], pm[1], pm[1] * 2, 2, 1, n_out)
             ops.affine2(dz1, c1, (b1.k1, b1.k2, b1.k3), dz1, amax_cell=self._cell(pre + "conv1", "b"))      # dc1 in place (+ its bound)
             self._conv_wgrad(pre + "conv1", X, dz1, B, H, W, Ho, Wo)
-            aux, even = dY, False
             if ds:
                 self._conv_wgrad(pre + "downsample.0", X, ddsc, B, H, W, Ho, Wo)
-                cd = self.convs[pre + "downsample.0"]
-                if cd.k == 1 and cd.stride == 2 and cd.pad == 0 and stride == 2 and H == 2 * Ho and W == 2 * Wo:
-                    # the 1x1 / stride 2 data gradient is non-zero at the even pixels only: computed at the small resolution
-                    # (a plain stride-1 product) and added there by the parity-class launches of conv1's data gradient
-                    aux = torch.empty((cd.cin, B * Ho * Wo), dtype=torch.float32, device=dev)
-                    if self._aux is not None:     # forked: ddsc has been ready since the apply pass; joined in front of conv1's data gradient
-                        self._aux.wait_event(ddsc_ready)
-                        with torch.cuda.stream(self._aux):
-                            ops.conv2d_gemm(ddsc, aux, self._w(pre + "downsample.0", True), cd.cout * cd.cin, cd.cin, B=B, Kc=cd.cout,
-                                            M=cd.cin, H_src=Ho, W_src=Wo, H_out=Ho, W_out=Wo, KH=1, KW=1, stride=1, pad=0, transposed=True)
-                        ddsc.record_stream(self._aux)
-                        torch.cuda.current_stream().wait_stream(self._aux)
-                    else:
-                        ops.conv2d_gemm(ddsc, aux, self._w(pre + "downsample.0", True), cd.cout * cd.cin, cd.cin, B=B, Kc=cd.cout,
-                                        M=cd.cin, H_src=Ho, W_src=Wo, H_out=Ho, W_out=Wo, KH=1, KW=1, stride=1, pad=0, transposed=True)
-                    even = True
+                if even:
+                    dense = lambda: ops.conv2d_gemm(
+                        ddsc, aux, self._w(pre + "downsample.0", True), cd.cout * cd.cin, cd.cin, B=B, Kc=cd.cout, M=cd.cin, H_src=Ho,
+                        W_src=Wo, H_out=Ho, W_out=Wo, KH=1, KW=1, stride=1, pad=0, transposed=True)
+                    # forked behind the apply pass only (ddsc has been ready since then); joined in front of conv1's data gradient
+                    self._fork(dense, ddsc, after=ddsc_ready)
+                    self._join()
                 else:
                     aux, _ = self._conv_dgrad(pre + "downsample.0", ddsc, B, H, W, Ho, Wo)
             dY, _ = self._conv_dgrad(pre + "conv1", dz1, B, H, W, Ho, Wo, epi=L.SAR_EPI_ADD, aux=aux, aux_even_pixels=even)
-            if bucket_cb is not None and pre.endswith(".0.") and pre[5] in "432":   # first block of layer 4 / 3 / 2: that stage is done
-                self._bucket_done({"4": 0, "3": 1, "2": 2}[pre[5]], bucket_cb)
-            elif bucket_cb is None and (self._slab_flush == "block" or (self._slab_flush == "bucket" and pre.endswith(".0.") and pre[5] in "432")):
-                self._flush_slabs()  # (experiment switch SAR_SLAB_FLUSH)
+            self._buckets_after_block(bidx, bucket_cb)      # first block of layer 4 / 3 / 2: that stage is done
         # stem: maxpool + relu + bn backward, then the 7x7 weight gradient (the image needs no gradient)
         bn0 = self.bn["bn1"]
         c0 = sv["c0"]
@@ -561,16 +508,9 @@ class ResNet18:
         self._bn_bwd("bn1", part, nparts, nparts * 2, 2, 1, B * sv["H1"] * sv["W1"])
         ops.affine2(dz0, c0, (bn0.k1, bn0.k2, bn0.k3), dz0)
         self._conv_wgrad("conv1", sv["x0"], dz0, B, sv["H"], sv["W"], sv["H1"], sv["W1"])
-        if bucket_cb is not None:
-            self._bucket_done(3, bucket_cb)                      # conv1 + bn1 + layer1
-            if self._side is not None:
-                torch.cuda.current_stream().wait_stream(self._side)
-        else:
-            self._flush_slabs()
-            if self._side is not None:
-                torch.cuda.current_stream().wait_stream(self._side)
-        if getattr(self, "_fc_forked", False):
-            torch.cuda.current_stream().wait_stream(self._aux)
+        self._finish_backward(bucket_cb)                         # the last bucket: conv1 + bn1 + layer1
+        if self._fc_forked:
+            self._join()
             self._fc_forked = False
         dx = None
         if need_dx:
@@ -578,7 +518,6 @@ class ResNet18:
             dx = torch.empty((B, 1, sv["H"], sv["W"]), dtype=torch.float32, device=dev)
             ops.conv2d_stem_dgrad(dz0, self._w("conv1"), dx, B=B, H=sv["H"], W=sv["W"], H_out=sv["H1"], W_out=sv["W1"],
                                   M=cv.cout, KH=cv.k, KW=cv.k, stride=cv.stride, pad=cv.pad)
-        self._saved = None
         return dx
 
     # ------------------------------------------------------------------ training step
@@ -599,7 +538,5 @@ class ResNet18:
         """torch.optim.Adam(lr) (main_spectrogram.py:106) over the flat buffers."""
         self._prepacked = None
         self.step_dev += 1.0
-        if getattr(self, "_lr_host", None) != float(lr):      # one launch less per step while the schedule holds the rate
-            self.lr_dev.fill_(float(lr))
-            self._lr_host = float(lr)
+        self._set_lr(lr)
         ops.adam(self.flat, self.adam_m, self.adam_v, self.grad, self.lr_dev, self.step_dev, betas[0], betas[1], eps)

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .engine import FlatEngine
 
 BN_EPS = 1e-3        # Keras BatchNormalization defaults (models/stgcn.py:27,37,56,111)
 BN_MOMENTUM = 0.99
@@ -71,7 +72,7 @@ class _BN:
         self.k1, self.k2, self.k3 = z(), z(), z()
 
 
-class STGCN:
+class STGCN(FlatEngine):
     # What a sibling engine (sar_amd/stgin.py, stpgcn.py, stgcn_ta.py) declares about itself; __init__ and the gates below read these:
     env_arithmetic = True      # built without `mfma`: DEFAULT_MFMA (the siblings are fp32)
     batched_slabs = True       # one slab reduction per gradient bucket (ops.SlabBatch) instead of one per weight gradient
@@ -124,14 +125,10 @@ class STGCN:
     # ------------------------------------------------------------------ the constructor's steps
     def _init_device(self, device, bone_pairs, motion):
         self.device = dev = torch.device(device)
-        # the weight-gradient stream; SAR_WGRAD_PRIO: its priority (torch convention: lower = more urgent; default 0 = same as
-        # the main chain)
-        self._side = (ops.shared_side_stream(dev, int(os.environ.get("SAR_WGRAD_PRIO", "0")))
-                      if dev.type == "cuda" and os.environ.get("SAR_WGRAD_STREAM", "1") == "1" else None)
-        self._slabs = ops.SlabBatch() if (ops.SLAB_BATCH and self.batched_slabs) else None
-        self._slab_flush = ops.SLAB_FLUSH
-        self._aux = ops.shared_aux_stream(dev) if (AUX_STREAM and self.third_stream and dev.type == "cuda") else None
-        self._aux_pending = self._bounds_forked = False
+        # the weight-gradient stream (SAR_WGRAD_STREAM=0: none); SAR_WGRAD_PRIO: its priority (default 0 = same as the main chain)
+        prio = int(os.environ.get("SAR_WGRAD_PRIO", "0")) if os.environ.get("SAR_WGRAD_STREAM", "1") == "1" else None
+        self._init_streams(prio, ops.SLAB_BATCH and self.batched_slabs, AUX_STREAM and self.third_stream)
+        self._aux_pending = False
         self.motion = bool(motion)   # motion stream (data_gen/gen_motion_data.py:24-27) of the joint / bone data, on the fly
         self.bone_parent = None
         if bone_pairs is not None:
@@ -179,22 +176,7 @@ class STGCN:
             self._add(pre + "res_bn.gamma", (f,)), self._add(pre + "res_bn.beta", (f,))
 
     def _allocate(self):
-        """flat storage: every offset is a multiple of 4 floats so that each weight view is 16-byte aligned (the GEMM kernels stage
-        weight rows as float4); a bias stays glued to its kernel because the weight-gradient slabs are reduced as one contiguous
-        [kernel | bias] range.  Returns the buffer's length."""
-        total, self.offsets = 0, {}
-        for k, shp in self.shapes.items():
-            n = int(np.prod(shp))
-            if k.endswith(".kernel"):
-                assert n % 4 == 0, k
-            self.offsets[k] = total
-            total += n if k.endswith(".kernel") else (n + 3) // 4 * 4
-        self.n_params = sum(int(np.prod(shp)) for shp in self.shapes.values())
-        z = lambda n: torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.flat, self.grad, self.velocity, self.lr_dev = z(total), z(total), z(total), z(1)
-        self._lr_host = None      # the value lr_dev holds (sgd_step skips the fill while the schedule keeps the rate); None = unknown
-        self.p = {k: self._view(self.flat, k) for k in self.shapes}
-        self.g = {k: self._view(self.grad, k) for k in self.shapes}
+        total = self._allocate_flat(("velocity",))
         if "adjacency_matrix" in self.p:
             self.A = self.p["adjacency_matrix"]          # the trainable copy (initialised from the graph in _init_params)
         return total
@@ -298,51 +280,11 @@ class STGCN:
         assert sum(h - l for _, l, h in out) == total and nb > 0
         return out
 
-    def _bucket_done(self, bi, cb):
-        """Every gradient of bucket bi has been ISSUED: weight gradients on the side stream, BatchNorm / bias gradients on the
-        main stream.  cb(bi, flat slice, events) may start the slice's all-reduce once the events have completed."""
-        _, lo, hi = self._buckets[bi]
-        events = []
-        self._flush_slabs()
-        if self._side is not None:
-            ev = torch.cuda.Event()
-            ev.record(self._side)
-            events.append(ev)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        events.append(ev)
-        cb(bi, self.grad[lo:hi], events)
-
-    def _flush_slabs(self):
-        """the slabs of every weight gradient issued since the last flush are summed by ONE launch on the weight-gradient stream
-        (ops.SlabBatch): before a bucket is handed to the all-reduce and at the end of backward()"""
-        if self._slabs is None:
-            return
-        if self._side is None:
-            self._slabs.flush()
-        else:
-            with torch.cuda.stream(self._side):
-                self._slabs.flush()
-
-    def _buckets_after_block(self, i, cb):
-        if cb is not None:
-            for bi, (blk, _, _) in enumerate(self._buckets):
-                if blk == i:
-                    self._bucket_done(bi, cb)
-        elif self._slabs is not None and (
-                self._slab_flush == "block" or (self._slab_flush == "bucket" and any(blk == i for blk, _, _ in self._buckets))):
-            self._flush_slabs()      # (experiment switch SAR_SLAB_FLUSH: more, smaller slab reductions than one at the end of backward)
-
     def _finish_backward(self, cb):
-        """common tail of backward(): nothing deferred is left behind, the side stream is joined, the remaining buckets go"""
+        """nothing deferred is left behind"""
         if self._deferred:
             self._flush_deferred()
-        if cb is not None:
-            self._buckets_after_block(-1, cb)
-        self._flush_slabs()
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side)      # every weight gradient is in self.grad
-        self._saved = None
+        super()._finish_backward(cb)
 
     # ------------------------------------------------------------------ a layer between two blocks (sar_amd/stpgcn.py)
     # Hook points of a sibling model that inserts a layer after block i: its parameters follow block i's in the flat buffer, its
@@ -391,10 +333,6 @@ class STGCN:
     def _add(self, name, shape):
         self.shapes[name] = tuple(shape)
 
-    def _view(self, flat, name):
-        o = self.offsets[name]
-        return flat[o:o + int(np.prod(self.shapes[name]))].view(self.shapes[name])
-
     def _init_params(self, seed):
         """models/stgcn.py:7-8 VarianceScaling(2, fan_out, truncated_normal); biases 0; BN gamma 1, beta 0."""
         gen = torch.Generator().manual_seed(seed)
@@ -415,19 +353,10 @@ class STGCN:
     def load_params(self, params):
         """params: dict name -> tensor in the oracle / Keras layouts (incl. optional moving stats, 'A' ignored)."""
         self._lr_host = None      # (a restored engine re-writes the device-side learning rate at its next step)
-        for k, v in params.items():
-            if k in self.p:
-                self.p[k].copy_(v.to(torch.float32).reshape(self.shapes[k]))
-            elif k.endswith(".moving_mean"):
-                self.bn[k[:-len(".moving_mean")]].moving_mean.copy_(v.to(torch.float32))
-            elif k.endswith(".moving_var"):
-                self.bn[k[:-len(".moving_var")]].moving_var.copy_(v.to(torch.float32))
+        super().load_params(params)
 
     def state_dict(self):
-        out = {k: v.detach().cpu().clone() for k, v in self.p.items()}
-        for k, b in self.bn.items():
-            out[k + ".moving_mean"] = b.moving_mean.cpu().clone()
-            out[k + ".moving_var"] = b.moving_var.cpu().clone()
+        out = super().state_dict()
         out["A"] = self.A.cpu().clone()
         return out
 
@@ -471,8 +400,7 @@ class STGCN:
             if self._aux is not None:
                 # term images, bound cells and the Samuelson cells (functions of gamma / beta and the sample counts) beside the data_bn
                 # stage and the 3-channel layer: joined in front of the first launch that reads an image or a cell (_join_aux)
-                self._aux.wait_stream(torch.cuda.current_stream())      # behind the optimizer step that produced self.flat
-                with torch.cuda.stream(self._aux):
+                def images():
                     self.spacked.refresh(self.flat)
                     self._cells.zero_()
                     Tb = T
@@ -480,6 +408,7 @@ class STGCN:
                         if self._cell_live("l%d.tcn.f" % bi_, "tfwd", "twgrad"):
                             ops.bn_bound(self.p["l%d.bn1.gamma" % bi_], self.p["l%d.bn1.beta" % bi_], B * Tb * V, self._cell(bi_, 0))
                         Tb = same_pad(Tb, KT, s_)[0]
+                self._fork(images)      # behind the optimizer step that produced self.flat
                 self._aux_pending = self._bounds_forked = True
             else:
                 self.spacked.refresh(self.flat)
@@ -598,7 +527,7 @@ class STGCN:
     def _join_aux(self):
         """the main chain waits for what forward() forked onto the third stream (once per step)"""
         if self._aux_pending:
-            torch.cuda.current_stream().wait_stream(self._aux)
+            self._join()
             self._aux_pending = False
 
     def _img(self, key):
@@ -641,26 +570,12 @@ class STGCN:
 
     # ------------------------------------------------------------------ backward
     def _off_critical_path(self, fn, *tensors):
-        """Weight-gradient kernels feed nothing but the optimizer: they run on a second stream, ordered after
-        everything issued so far, so that the MFMA-bound reductions overlap the HBM-bound BatchNorm / ReLU passes of
-        the main chain.  `tensors` are the inputs whose memory the caching allocator must not hand out again before
-        the side stream is done with them.  On by default (SAR_WGRAD_STREAM=0 turns it off): measured +3.5 % clips/s at
-        bs = 64 in fp32 -- the MFMA kernels fill the register file, so only part of the element-wise work can co-reside.
-        Per-kernel timings of overlapping kernels are inflated; bench.py therefore also reports the dominant family
-        measured in a short pass with the side stream off (roofline.isolated)."""
-        if self._side is None:
-            fn()
-            return
-        if self._wgrad_defer() and not self._flushing:   # see _WGRAD_DEFER_ENV above
+        """fn() on the weight-gradient stream (_on_side), at once or -- see _WGRAD_DEFER_ENV above -- when the block's data
+        gradients have been issued (_flush_deferred)"""
+        if self._side is not None and self._wgrad_defer() and not self._flushing:
             self._deferred.append((fn, tensors))
-            return
-        main = torch.cuda.current_stream()
-        self._side.wait_stream(main)
-        with torch.cuda.stream(self._side):
-            fn()
-        for t in tensors:
-            if t is not None:
-                t.record_stream(self._side)
+        else:
+            self._on_side(fn, *tensors)
 
     def _wgrad_defer(self):
         return (not self.cn8) if _WGRAD_DEFER_ENV is None else _WGRAD_DEFER_ENV == "1"
@@ -917,9 +832,7 @@ class STGCN:
 
     def sgd_step(self, lr, momentum=0.9):
         """tf.keras SGD(momentum, nesterov=True) over the flat buffers (main_gnn.py:312-314)."""
-        if self._lr_host != float(lr):      # one launch less per step while the schedule holds the rate
-            self.lr_dev.fill_(float(lr))
-            self._lr_host = float(lr)
+        self._set_lr(lr)
         ops.sgd_nesterov(self.flat, self.velocity, self.grad, self.lr_dev, momentum)
 
     def predict(self, x):

@@ -4,7 +4,12 @@ a fixed order, so logits, loss and every gradient must be BITWISE identical betw
 race (LDS hazard, missing barrier).  Usage: python tools/determinism_check.py [--reps 5] [--batch 64]
 
 --digest prints, per mode, the SHA-256 of logits, loss, grad and flat after each of two loss_and_grad + sgd_step rounds and of
-predict(x): two commits that print the same lines on the same machine and library compute the same steps."""
+predict(x): two commits that print the same lines on the same machine and library compute the same steps.  The modes resnet,
+resnet_f32_split and resnet_f32_split_bf16x6 digest Path B's classifier (num_filters 64, a fixed (4, 1, 64, 64) input: the smallest
+at which all four stages, the down-sampling branches, the K-split of the small feature maps and the stride-2 parity classes run):
+loss_and_grad(need_dx=True) + adam_step, dx as well, and the logits of forward(training=False).  For these and for fp32 / bf16 a
+second pass on a fresh engine hands its gradient buckets to a callback that records (bucket, lo, hi): the hand-over order is
+printed and the digests once more ("<mode>+buckets")."""
 import argparse
 import hashlib
 import os
@@ -24,16 +29,23 @@ def sha(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
 
-def digest(mode, eng, x, y):
+def digest(mode, eng, x, y, record_buckets=False):
+    resnet, kw, order = mode.startswith("resnet"), {}, []
+    if record_buckets:
+        mode += "+buckets"
+        kw["bucket_cb"] = lambda bi, flat, events: order.append(
+            (bi, (flat.data_ptr() - eng.grad.data_ptr()) // 4, (flat.data_ptr() - eng.grad.data_ptr()) // 4 + flat.numel()))
     for step in range(2):
-        logits, loss = eng.loss_and_grad(x, y)[:2]
-        eng.sgd_step(0.1)
+        out = eng.loss_and_grad(x, y, need_dx=True, **kw) if resnet else eng.loss_and_grad(x, y, **kw)
+        eng.adam_step(1e-3) if resnet else eng.sgd_step(0.1)
         torch.cuda.synchronize()
-        for name, t in (("logits", logits), ("loss", loss), ("grad", eng.grad), ("flat", eng.flat)):
+        for name, t in (("logits", out[0]), ("loss", out[1])) + ((("dx", out[2]),) if resnet else ()) + (("grad", eng.grad), ("flat", eng.flat)):
             print("%s step%d %s %s" % (mode, step, name, sha(t)))
-    probs = eng.predict(x)
+    probs = eng.forward(x, training=False) if resnet else eng.predict(x)
     torch.cuda.synchronize()
     print("%s predict %s" % (mode, sha(probs)))
+    if record_buckets:
+        print("%s order %s" % (mode, ";".join("%d:%d-%d" % o for o in order)))
 
 
 def main():
@@ -45,13 +57,18 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     total_bad = 0
-    for mode in a.modes.split(","):
+    modes = a.modes.split(",")
+    if a.digest:
+        modes += [m + "+buckets" for m in modes if m in ("fp32", "bf16") or m.startswith("resnet")]
+    for mode in modes:
+        mode, buckets = mode.split("+")[0], mode.endswith("+buckets")
         bad = 0
-        if mode == "resnet":      # Path B's classifier at its bench shape (bs 32, 256 x 256 spectrograms)
+        if mode.startswith("resnet"):      # Path B's classifier at its bench shape (bs 32, 256 x 256 spectrograms; --digest: see above)
             from sar_amd.resnet import ResNet18
-            eng = ResNet18(num_classes=60, num_filters=64, device=dev, seed=0)
+            eng = ResNet18(num_classes=60, num_filters=64, device=dev, seed=0, mfma=mode[7:] or None)
             g = torch.Generator(device=dev).manual_seed(5)
-            x, y = torch.randn((32, 1, 256, 256), generator=g, device=dev), torch.randint(0, 60, (32,), generator=g, device=dev)
+            n, hw = (4, 64) if a.digest else (32, 256)
+            x, y = torch.randn((n, 1, hw, hw), generator=g, device=dev), torch.randint(0, 60, (n,), generator=g, device=dev)
         elif mode == "stgin":
             from sar_amd.stgin import STGIN
             eng = STGIN(num_classes=60, device=dev, seed=0)
@@ -70,7 +87,7 @@ def main():
             eng = STGCN(num_classes=60, device=dev, seed=0, mfma=mode)
             x, y = synthetic_clips(a.batch, dev, seed=3, num_classes=60)
         if a.digest:
-            digest(mode, eng, x, y)
+            digest(mode, eng, x, y, buckets)
             continue
         state = {k: v.clone() for k, v in eng.state_dict().items()}
         ref = None
