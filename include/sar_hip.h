@@ -833,6 +833,60 @@ int sar_cn8_to_cn(const void* x, int64_t ld_x, float* out, int64_t ld_out, int C
 int sar_pre_normalize_f32(const float* x, float* out, int N, int T, int V, int M, int z0, int z1, int x0, int x1, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * TemporalSampler (models/lstm_sampler.py:1-27): a stack of Keras LSTM layers scores every frame, the top_k best frames are
+ * gathered and scaled by their scores.  csrc/lstm.hip, fp32.  The stack's activations are CN matrices [rows][ld] with TIME-MAJOR
+ * columns t*N + n (sequence n, step t): every ld >= T*N, no alignment beyond the element, columns past T*N are neither read nor
+ * written.  Every limit is checked before anything is launched (SAR_E_ARG / SAR_E_UNSUP); no atomics, repeated launches are
+ * bitwise equal.
+ *   sar_lstm_fwd_f32   models/lstm_sampler.py:6-9 (tf.keras.layers.LSTM(u, return_sequences=True), zero initial state, gate order
+ *                      i, f, c, o along the 4u axis, tanh / sigmoid): with zin [4u][T*N] = kernel^T x + bias (the caller's 1x1
+ *                      product) and U = recurrent_kernel [u][4u] contiguous (Keras layout),
+ *                        z_t = zin_t + U^T h_{t-1};  i, f, o = sigmoid(z_i, z_f, z_o), g = tanh(z_c);
+ *                        c_t = f c_{t-1} + i g;  h_t = o tanh(c_t)                 -> h [u][T*N]
+ *                      One launch walks all T steps: a workgroup owns 16 sequences, keeps U in registers (fp32 MFMA operands,
+ *                      v_mfma_f32_16x16x4_f32: exact fp32) and c in registers, and exchanges h_{t-1} through LDS.  gates
+ *                      [4u][T*N] (the POST-activation i, f, g, o) and c [u][T*N] (the cell state itself; tanh(c) is recomputed)
+ *                      are written when both are non-NULL (both NULL: the inference form).  A sequence's result does not depend
+ *                      on which other sequences share its workgroup or launch, bit for bit.
+ *                      1 <= u <= 128 (larger: SAR_E_UNSUP), N >= 1, T >= 1, T*N < 2^31; u need not be a multiple of anything.
+ *   sar_lstm_bwd_f32   back-propagation through time of the same layer, t = T-1 .. 0: from dh [u][T*N] (the gradient arriving at h
+ *                      from above), the saved gates and c, and U:  dz [4u][T*N], the gradient at z (pre-activation, rows i, f, c,
+ *                      o); dh_{t-1} += U dz_t and dc are carried on chip.  Same residency scheme and limits.  The parameter
+ *                      gradients are products of dz: d kernel / d bias from (x, dz), d recurrent_kernel = sum_t h_{t-1} dz_t^T from
+ *                      the views h[:, 0 : (T-1) N] and dz[:, N : T N] (sar_conv_wgrad_f32), dx = kernel dz (sar_conv_gemm_f32).
+ *   sar_topk_desc_f32  models/lstm_sampler.py:21-23 (tf.math.top_k; sorted=False leaves the order open, fixed here): per sequence
+ *                      the k best of the T scores scores[n*stride_n + t*stride_t], DESCENDING by score, equal scores in ASCENDING
+ *                      frame index -> values [N][k], idx [N][k]; inv [N][T] = j where frame t is idx[n][j], else -1.  One
+ *                      workgroup per sequence sorts (score, index) keys in LDS.  1 <= k <= T <= 2048 (T larger: SAR_E_UNSUP).
+ *                      With NaN among a sequence's scores its order is unspecified, but idx still holds k distinct frames in
+ *                      [0, T) and inv is its inverse.
+ *   sar_frame_gather_f32      models/lstm_sampler.py:24-26: out[n, c, j, v] = x[n, c, idx[n, j], v] * values[n, j]; x (N, C, T, V)
+ *                      and out (N, C, k, V) contiguous (NCHW).  idx entries outside [0, T) are clamped, never followed.
+ *   sar_frame_gather_bwd_f32  its gradients, one wave per (n, t), j = inv[n, t]:
+ *                        dvalues[n, j] = sum_{c,v} dout[n, c, j, v] x[n, c, t, v]   (fixed order)
+ *                        dscores[n*stride_n + t*stride_t] = dvalues[n, j], 0 where inv = -1
+ *                        dx[n, c, t, v] = dout[n, c, j, v] values[n, j], 0 where inv = -1     (only when dx != NULL)
+ *                      Every element of dvalues, dscores and dx is written exactly once: no memset.
+ *   sar_lstm_pack_f32        models/lstm_sampler.py:17-18: X[v*C + c][t*N + n] = x[n, c, t, v]  (x (N, C, T, V) contiguous, X a CN
+ *                      matrix of V*C rows); T, C <= 65535.
+ *   sar_lstm_unpack_add_f32  the reverse, ADDING: x[n, c, t, v] += X[v*C + c][t*N + n] (the LSTM-path input gradient into the
+ *                      gather-path one).
+ * ------------------------------------------------------------------------------------------------ */
+int sar_lstm_fwd_f32(const float* zin, int64_t ld_zin, const float* U, float* h, int64_t ld_h, float* gates, int64_t ld_gates,
+                     float* c, int64_t ld_c, int u, int N, int T, sar_stream_t s);
+int sar_lstm_bwd_f32(const float* dh, int64_t ld_dh, const float* gates, int64_t ld_gates, const float* c, int64_t ld_c,
+                     const float* U, float* dz, int64_t ld_dz, int u, int N, int T, sar_stream_t s);
+int sar_topk_desc_f32(const float* scores, int64_t stride_n, int64_t stride_t, int N, int T, int k, float* values, int32_t* idx,
+                      int32_t* inv, sar_stream_t s);
+int sar_frame_gather_f32(const float* x, const int32_t* idx, const float* values, float* out, int N, int C, int T, int V, int k,
+                         sar_stream_t s);
+int sar_frame_gather_bwd_f32(const float* x, const float* dout, const float* values, const int32_t* inv, float* dvalues,
+                             float* dscores, int64_t stride_n, int64_t stride_t, float* dx, int N, int C, int T, int V, int k,
+                             sar_stream_t s);
+int sar_lstm_pack_f32(const float* x, float* X, int64_t ld, int N, int C, int T, int V, sar_stream_t s);
+int sar_lstm_unpack_add_f32(const float* X, int64_t ld, float* x, int N, int C, int T, int V, sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * Box calibration (csrc/box_probe.hip; bench.py's "box" object -- no reference counterpart, measurement only): what the box
  * this process landed on sustains, so that a line's `frac` (against the guide's peaks) can be read next to `frac_of_box`.
  *   sar_box_mfma        dense loop of one matrix instruction: kind 0 = v_mfma_f32_32x32x2_f32, 1 = v_mfma_f32_32x32x16_f16,

@@ -1,6 +1,7 @@
 """Drop-in for the reference's `models` package (models/__init__.py:1-6).  Only the north-star models are
 provided: `models.stgcn` (ST-GCN), its siblings `models.stgin` (graph isomorphism convolution), `models.stpgcn`
 (ST-GCN with a projection graph convolution after the first block) and `models.stgcn_debug` (ST-GCN with a trainable
-adjacency per frame and per block, the model --freeze-graph-until acts on), and `models.resnet` /
-`models.resnet18` (VirtualRadar + ResNet-18).
+adjacency per frame and per block, the model --freeze-graph-until acts on), `models.resnet` /
+`models.resnet18` (VirtualRadar + ResNet-18), the layer-level modules of `models.gcn`, and `models.lstm_sampler`
+(`TemporalSampler`: an LSTM stack scores the frames of a clip, the top_k best are gathered and scaled by their scores).
 Sub-modules are imported lazily so that `import models` works on a CPU-only box."""

@@ -213,6 +213,14 @@ SIGNATURES = {
     "sar_cn8_to_cn": (_i, [_fp, _i64, _fp, _i64, _i, _i64, _fp]),
     # pre-normalisation of raw clips (csrc/prenorm.hip)
     "sar_pre_normalize_f32": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _fp]),
+    # TemporalSampler: LSTM recurrence, top-k, frame gather (csrc/lstm.hip)
+    "sar_lstm_fwd_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _fp, _i64, _fp, _i64, _i, _i, _i, _fp]),
+    "sar_lstm_bwd_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _i64, _i, _i, _i, _fp]),
+    "sar_topk_desc_f32": (_i, [_fp, _i64, _i64, _i, _i, _i, _fp, _fp, _fp, _fp]),
+    "sar_frame_gather_f32": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp]),
+    "sar_frame_gather_bwd_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i64, _i64, _fp, _i, _i, _i, _i, _i, _fp]),
+    "sar_lstm_pack_f32": (_i, [_fp, _fp, _i64, _i, _i, _i, _i, _fp]),
+    "sar_lstm_unpack_add_f32": (_i, [_fp, _i64, _fp, _i, _i, _i, _i, _fp]),
     # box calibration (bench.py "box"; csrc/box_probe.hip)
     "sar_box_mfma": (_i, [_i, _i, _i, _fp, _fp, _fp]),
     "sar_box_mfma_flops": (_i64, [_i, _i, _i]),

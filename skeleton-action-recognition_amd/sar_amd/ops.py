@@ -808,6 +808,79 @@ def gin_sample_eps_grad(x, dout, deps, F, V, N, scratch=None):
 
 
 # ------------------------------------------------------------------------------------------------ graph isomorphism conv
+# ------------------------------------------------------------------------------------------------ TemporalSampler (csrc/lstm.hip)
+def _i32(t, shape):
+    assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
+        "need a contiguous cuda int32 tensor of shape %s" % (tuple(shape),)
+    return t
+
+
+def lstm_fwd(zin, U, h, u, N, T, gates=None, c=None):
+    """h [u][T N] of one Keras LSTM layer from zin [4u][T N] = kernel^T x + bias and U = recurrent_kernel (u, 4u), all T steps in one
+    launch (sar_lstm_fwd_f32); time-major columns t N + n.  gates [4u][T N] (post-activation i, f, g, o) and c [u][T N] are saved
+    when given (both or neither)."""
+    assert U.is_contiguous() and tuple(U.shape) == (u, 4 * u), "U must be the contiguous (u, 4u) recurrent kernel"
+    assert zin.shape[0] == 4 * u and h.shape[0] == u and (gates is None or gates.shape[0] == 4 * u) and (c is None or c.shape[0] == u)
+    check(L.load().sar_lstm_fwd_f32(ptr(_f32(zin)), zin.stride(0), ptr(_f32(U)), ptr(_f32(h)), h.stride(0), ptr(_f32(gates)),
+                                    gates.stride(0) if gates is not None else 0, ptr(_f32(c)), c.stride(0) if c is not None else 0,
+                                    u, N, T, stream_ptr()), "sar_lstm_fwd_f32")
+
+
+def lstm_bwd(dh, gates, c, U, dz, u, N, T):
+    """dz [4u][T N] (the gradient at the pre-activations, rows i, f, c, o) from dh [u][T N] (the gradient arriving at h from above),
+    the saved gates and c, and U: back-propagation through time in one launch (sar_lstm_bwd_f32)"""
+    assert U.is_contiguous() and tuple(U.shape) == (u, 4 * u), "U must be the contiguous (u, 4u) recurrent kernel"
+    assert dh.shape[0] == u and gates.shape[0] == 4 * u and c.shape[0] == u and dz.shape[0] == 4 * u
+    check(L.load().sar_lstm_bwd_f32(ptr(_f32(dh)), dh.stride(0), ptr(_f32(gates)), gates.stride(0), ptr(_f32(c)), c.stride(0),
+                                    ptr(_f32(U)), ptr(_f32(dz)), dz.stride(0), u, N, T, stream_ptr()), "sar_lstm_bwd_f32")
+
+
+def topk_desc(scores, stride_n, stride_t, N, T, k, values, idx, inv):
+    """per sequence the k best of scores[n stride_n + t stride_t], descending, equal scores in ascending frame index
+    (sar_topk_desc_f32) -> values (N, k) float32, idx (N, k) int32, inv (N, T) int32 (j where frame t = idx[n, j], else -1)"""
+    assert scores.is_cuda and scores.dtype == torch.float32
+    assert values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and tuple(values.shape) == (N, k)
+    check(L.load().sar_topk_desc_f32(ptr(scores), stride_n, stride_t, N, T, k, ptr(values), ptr(_i32(idx, (N, k))),
+                                     ptr(_i32(inv, (N, T))), stream_ptr()), "sar_topk_desc_f32")
+
+
+def frame_gather(x, idx, values, out):
+    """out (N, C, k, V) = x (N, C, T, V) at the frames idx (N, k), scaled by values (N, k) (sar_frame_gather_f32)"""
+    N, C, T, V = x.shape
+    k = idx.shape[1]
+    assert x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (N, C, k, V) and values.is_contiguous()
+    assert tuple(values.shape) == (N, k)
+    check(L.load().sar_frame_gather_f32(ptr(_f32(x)), ptr(_i32(idx, (N, k))), ptr(_f32(values)), ptr(_f32(out)), N, C, T, V, k,
+                                        stream_ptr()), "sar_frame_gather_f32")
+
+
+def frame_gather_bwd(x, dout, values, inv, dvalues, dscores, stride_n, stride_t, dx=None):
+    """the gather's gradients (sar_frame_gather_bwd_f32): dvalues (N, k), dscores in the scores' strided layout, dx (N, C, T, V) when
+    given; every element written once"""
+    N, C, T, V = x.shape
+    k = dout.shape[2]
+    assert x.is_contiguous() and dout.is_contiguous() and tuple(dout.shape) == (N, C, k, V) and (dx is None or dx.is_contiguous())
+    assert values.is_contiguous() and dvalues.is_contiguous() and tuple(values.shape) == (N, k) == tuple(dvalues.shape)
+    assert dscores.is_cuda and dscores.dtype == torch.float32 and (dx is None or dx.shape == x.shape)
+    check(L.load().sar_frame_gather_bwd_f32(ptr(_f32(x)), ptr(_f32(dout)), ptr(_f32(values)), ptr(_i32(inv, (N, T))), ptr(_f32(dvalues)),
+                                            ptr(dscores), stride_n, stride_t, ptr(_f32(dx)), N, C, T, V, k, stream_ptr()),
+          "sar_frame_gather_bwd_f32")
+
+
+def lstm_pack(x, X):
+    """X[v C + c][t N + n] = x[n, c, t, v] (sar_lstm_pack_f32): the LSTM stack's input matrix of a contiguous (N, C, T, V) tensor"""
+    N, C, T, V = x.shape
+    assert x.is_contiguous() and X.shape[0] == V * C
+    check(L.load().sar_lstm_pack_f32(ptr(_f32(x)), ptr(_f32(X)), X.stride(0), N, C, T, V, stream_ptr()), "sar_lstm_pack_f32")
+
+
+def lstm_unpack_add(X, x):
+    """x[n, c, t, v] += X[v C + c][t N + n] (sar_lstm_unpack_add_f32)"""
+    N, C, T, V = x.shape
+    assert x.is_contiguous() and X.shape[0] == V * C
+    check(L.load().sar_lstm_unpack_add_f32(ptr(_f32(X)), X.stride(0), ptr(_f32(x)), N, C, T, V, stream_ptr()), "sar_lstm_unpack_add_f32")
+
+
 def conv_gemm_nparts(B, V, T_src, T_out, Kc, M, taps=1, stride=1, pad=0, transposed=False, epi=L.SAR_EPI_STATS):
     """partial sums per output row that sar_conv_gemm_f32 (TEMPORAL) writes for this geometry"""
     d = ConvDesc()
