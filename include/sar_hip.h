@@ -751,6 +751,59 @@ int sar_pgc_param_grad_f32(const float* colsum, const float* pooled, const float
                            sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * ProjectionGraphPool(J) of ST-PGCNP (models/stpgcnp.py:11-38), fp32 (csrc/pgpool.hip).  Sizes are arguments: 1 <= C, J <=
+ * SAR_PGPOOL_MAX, P >= 1 columns per sample, B <= 65535, B * P < 2^31; anything else is SAR_E_UNSUP before a launch.
+ * x / dx: CN layout [C][ld >= B*P], column b*P + p.  q / dq / dl: [J][ld >= B*P] (row j = vertex j).  centers / variance [C][J]
+ * (Keras shape (1, C, 1, J)); tab [4][C][J] = r | r^2 | r^2 centers | s with s = sigmoid(variance), r = 1 / s.  Per-sample tensors
+ * S / zp / zn / dz / dzn / dS / M1 / M2 [B][C][J], A_out / dA [B][J][J], qs / dqs / M0 [B][J], n2 [B][C] are contiguous.
+ * clamp: [B*P][sar_pgpool_clamp_words(J)] 32-bit words, bit j % 32 of word j / 32 set where the 1e-12 clamp of models/stpgcnp.py:30
+ * held (no gradient passes).  No tensor with both a P and a C x J extent exists; every sum over columns is ONE workgroup's
+ * fixed-order sum (one partial whatever P is): no atomics, bitwise deterministic, and a sample's results do not depend on the
+ * other samples of the batch.  A vertex with qs == 0 gives 0 / 0 as in the reference.
+ *   sar_pgpool_prep_f32          tab from centers / variance  -- models/stpgcnp.py:28 (1 / sigmoid(variance))
+ *   sar_pgpool_assign_f32        q = softmax_j(-0.5 max(sum_c ((x - centers) r)^2, 1e-12)), clamp  -- models/stpgcnp.py:28-31; the
+ *                                distance in difference form, 16-channel fp32 blocks summed in fp64, the column's reference
+ *                                logit subtracted before rounding
+ *   sar_pgpool_moment_f32        out[b] = x_b w_b^T (square != 0: x_b^2 w_b^T), w [J][ld_w]: with w = q the S of
+ *                                models/stpgcnp.py:33 (sum_p q z = (S - centers qs) r), with w = dl the sums of the parameter gradients
+ *   sar_pgpool_rowsum_f32        out[b][j] = sum_p w[j][b*P + p]  -- models/stpgcnp.py:34 (qs)
+ *   sar_pgpool_normalize_f32     zp = (S - centers qs) / (s qs) written over S, n2 = sum_j zp^2, zn = zp / sqrt(max(n2, 1e-12))
+ *                                -- models/stpgcnp.py:33-35 (l2_normalize over the last axis)
+ *   sar_pgpool_gram_f32          A_out[b] = zn_b^T zn_b  -- models/stpgcnp.py:37
+ *   sar_pgpool_gram_bwd_f32      dzn = dz + zn (dA + dA^T)  (dzn may not alias dz, zn or dA)
+ *   sar_pgpool_normalize_bwd_f32 dS = dzp / (s qs), dzp = (dzn - zn <dzn, zn>_j) / sqrt(n2) (dzn / 1e-6 where n2 <= 1e-12);
+ *                                dqs[b][j] = -sum_c dS (zp s + centers)
+ *   sar_pgpool_dq_f32            dq[j][b*P + p] = sum_c dS[b][c][j] x[c][b*P + p] + dqs[b][j]
+ *   sar_pgpool_softmax_bwd_f32   dq <- dl = q (dq - sum_j q dq), 0 where clamp is set
+ *   sar_pgpool_dx_f32            dx = dS q + (r^2 centers) dl - x * (r^2 dl)  (= dS q - sum_j dl r^2 (x - centers); dx may not be x)
+ *   sar_pgpool_param_grad_f32    dcenters = sum_b [r^2 (M1 - centers M0) - dS qs], ds = sum_b [r^3 (M2 - 2 centers M1 + centers^2 M0)
+ *                                - dS qs zp], dvariance = ds s (1 - s); M0 = rowsum(dl), M1 = moment(x, dl), M2 = moment(x^2, dl)
+ * ------------------------------------------------------------------------------------------------ */
+#define SAR_PGPOOL_MAX 512
+int sar_pgpool_clamp_words(int J);
+int sar_pgpool_prep_f32(const float* centers, const float* variance, int C, int J, float* tab, sar_stream_t s);
+int sar_pgpool_assign_f32(const float* x, int64_t ld_x, int B, int64_t P, int C, int J, const float* centers, const float* tab,
+                          float* q, int64_t ld_q, uint32_t* clamp, sar_stream_t s);
+int sar_pgpool_moment_f32(const float* x, int64_t ld_x, const float* w, int64_t ld_w, int B, int64_t P, int C, int J, int square,
+                          float* out, sar_stream_t s);
+int sar_pgpool_rowsum_f32(const float* w, int64_t ld_w, int B, int64_t P, int J, float* out, sar_stream_t s);
+int sar_pgpool_normalize_f32(float* S, const float* qs, const float* centers, const float* tab, int B, int C, int J, float* zn,
+                             float* n2, sar_stream_t s);
+int sar_pgpool_gram_f32(const float* zn, int B, int C, int J, float* A_out, sar_stream_t s);
+int sar_pgpool_gram_bwd_f32(const float* zn, const float* dz, const float* dA, int B, int C, int J, float* dzn, sar_stream_t s);
+int sar_pgpool_normalize_bwd_f32(const float* dzn, const float* zn, const float* zp, const float* n2, const float* qs,
+                                 const float* centers, const float* tab, int B, int C, int J, float* dS, float* dqs, sar_stream_t s);
+int sar_pgpool_dq_f32(const float* x, int64_t ld_x, const float* dS, const float* dqs, int B, int64_t P, int C, int J, float* dq,
+                      int64_t ld_dq, sar_stream_t s);
+int sar_pgpool_softmax_bwd_f32(const float* q, int64_t ld_q, const uint32_t* clamp, int B, int64_t P, int J, float* dq, int64_t ld_dq,
+                               sar_stream_t s);
+int sar_pgpool_dx_f32(const float* x, int64_t ld_x, const float* dS, const float* q, int64_t ld_q, const float* dl, int64_t ld_dl,
+                      const float* tab, int B, int64_t P, int C, int J, float* dx, int64_t ld_dx, sar_stream_t s);
+int sar_pgpool_param_grad_f32(const float* M0, const float* M1, const float* M2, const float* dS, const float* qs, const float* zp,
+                              const float* centers, const float* tab, int B, int C, int J, float* dcenters, float* dvariance,
+                              sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 configuration (bf16 activations in HBM, bf16 MFMA operands, fp32 accumulation, fp32
  * BatchNorm statistics, fp32 master weights).
  *

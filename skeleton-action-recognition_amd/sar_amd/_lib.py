@@ -175,6 +175,20 @@ SIGNATURES = {
     "sar_pgc_small_bwd_f32": (_i, [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp]),
     "sar_pgc_bwd_column_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, _i, _i64, _fp, _i64, _fp, _fp]),
     "sar_pgc_param_grad_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp]),
+    # ST-PGCNP projection graph pooling (csrc/pgpool.hip)
+    "sar_pgpool_clamp_words": (_i, [_i]),
+    "sar_pgpool_prep_f32": (_i, [_fp, _fp, _i, _i, _fp, _fp]),
+    "sar_pgpool_assign_f32": (_i, [_fp, _i64, _i, _i64, _i, _i, _fp, _fp, _fp, _i64, _fp, _fp]),
+    "sar_pgpool_moment_f32": (_i, [_fp, _i64, _fp, _i64, _i, _i64, _i, _i, _i, _fp, _fp]),
+    "sar_pgpool_rowsum_f32": (_i, [_fp, _i64, _i, _i64, _i, _fp, _fp]),
+    "sar_pgpool_normalize_f32": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
+    "sar_pgpool_gram_f32": (_i, [_fp, _i, _i, _i, _fp, _fp]),
+    "sar_pgpool_gram_bwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _i, _fp, _fp]),
+    "sar_pgpool_normalize_bwd_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
+    "sar_pgpool_dq_f32": (_i, [_fp, _i64, _fp, _fp, _i, _i64, _i, _i, _fp, _i64, _fp]),
+    "sar_pgpool_softmax_bwd_f32": (_i, [_fp, _i64, _fp, _i, _i64, _i, _fp, _i64, _fp]),
+    "sar_pgpool_dx_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _fp, _i64, _fp, _i, _i64, _i, _i, _fp, _i64, _fp]),
+    "sar_pgpool_param_grad_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
     "sar_graph_dense_nparts": (_i, [_i64]),
     "sar_graph_dense_fwd_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _i64, _fp, _fp, _i64, _fp]),
     "sar_graph_dense_bwd_data_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _i64, _fp]),

@@ -1013,6 +1013,90 @@ def pgc_backward(x, dout, q, saved, B, P, centers, variance, W, dx, g_centers, g
                                      stream_ptr()), "sar_pgc_param_grad_f32")
 
 
+# ------------------------------------------------------------------------------------------------ ST-PGCNP projection graph pooling
+# csrc/pgpool.hip (include/sar_hip.h: ProjectionGraphPool).  x / dx: CN [C][B*P]; q / dq: [J][B*P]; centers / variance: C * J elements
+PGPOOL_MAX = 512
+
+
+def _pgpool_check(B, P, C, J, cn=(), dense=()):
+    """ValueError before the library is touched: sizes the kernels are not built for, operands that are not float32 CUDA tensors,
+    `cn` operands (2-D, B * P live columns) without a unit column stride, `dense` operands that are not contiguous"""
+    if not (1 <= C <= PGPOOL_MAX and 1 <= J <= PGPOOL_MAX):
+        raise ValueError("ProjectionGraphPool is built for 1 <= C <= %d and 1 <= J <= %d (got C = %d, J = %d)" % (PGPOOL_MAX, PGPOOL_MAX, C, J))
+    if B < 1 or P < 1:
+        raise ValueError("ProjectionGraphPool needs B >= 1 and P >= 1 (got B = %d, P = %d)" % (B, P))
+    for t in cn:
+        if not (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.shape[1] == B * P):
+            raise ValueError("a CN operand must be a 2-D tensor of B * P = %d columns, contiguous or a row-strided view with a unit "
+                             "column stride (got shape %s, strides %s)" % (B * P, tuple(t.shape), tuple(t.stride())))
+    for t in dense:
+        if not t.is_contiguous():
+            raise ValueError("a per-sample or parameter operand must be contiguous (got shape %s, strides %s)"
+                             % (tuple(t.shape), tuple(t.stride())))
+    for t in tuple(cn) + tuple(dense):
+        if not (t.is_cuda and t.dtype in (torch.float32, torch.int32)):
+            raise ValueError("operands must be float32 CUDA tensors (got %s on %s)" % (t.dtype, t.device))
+
+
+def pgpool_forward(x, B, P, centers, variance):
+    """ProjectionGraphPool forward (models/stpgcnp.py:22-38) of the CN matrix x [C][B*P] (may be a row-strided view).  Returns
+    (zn (B, C, J), A_out (B, J, J), saved): saved = (q [J][B*P], clamp bits, zp (B, C, J), qs (B, J), n2 (B, C), tab (4, C, J)) is what
+    pgpool_backward needs."""
+    C, J = x.shape[0], centers.numel() // max(x.shape[0], 1)
+    dev = x.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    _pgpool_check(B, P, C, J, cn=(x,), dense=(centers, variance))
+    if centers.numel() != C * J or variance.numel() != C * J:
+        raise ValueError("centers / variance must hold C * J = %d elements each" % (C * J))
+    lib = L.load()
+    q, tab, S, zn, A = new(J, B * P), new(4, C, J), new(B, C, J), new(B, C, J), new(B, J, J)
+    qs, n2 = new(B, J), new(B, C)
+    clamp = torch.empty((B * P, lib.sar_pgpool_clamp_words(J)), dtype=torch.int32, device=dev)
+    st = stream_ptr()
+    check(lib.sar_pgpool_prep_f32(ptr(centers), ptr(variance), C, J, ptr(tab), st), "sar_pgpool_prep_f32")
+    check(lib.sar_pgpool_assign_f32(ptr(x), x.stride(0), B, P, C, J, ptr(centers), ptr(tab), ptr(q), q.stride(0), ptr(clamp), st),
+          "sar_pgpool_assign_f32")
+    check(lib.sar_pgpool_moment_f32(ptr(x), x.stride(0), ptr(q), q.stride(0), B, P, C, J, 0, ptr(S), st), "sar_pgpool_moment_f32")
+    check(lib.sar_pgpool_rowsum_f32(ptr(q), q.stride(0), B, P, J, ptr(qs), st), "sar_pgpool_rowsum_f32")
+    check(lib.sar_pgpool_normalize_f32(ptr(S), ptr(qs), ptr(centers), ptr(tab), B, C, J, ptr(zn), ptr(n2), st), "sar_pgpool_normalize_f32")
+    check(lib.sar_pgpool_gram_f32(ptr(zn), B, C, J, ptr(A), st), "sar_pgpool_gram_f32")
+    return zn, A, (q, clamp, S, qs, n2, tab)      # (S now holds zp)
+
+
+def pgpool_backward(x, B, P, centers, zn, saved, dz, dA, dx, dcenters, dvariance):
+    """Backward of pgpool_forward from dz (B, C, J) and dA (B, J, J) (either may be None = zero): dx [C][B*P], dcenters / dvariance
+    (C * J elements each) are written.  Returns dl [J][B*P]."""
+    q, clamp, zp, qs, n2, tab = saved
+    C, J = x.shape[0], q.shape[0]
+    dev = x.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    if dz is None:
+        dz = torch.zeros((B, C, J), dtype=torch.float32, device=dev)
+    if dA is None:
+        dA = torch.zeros((B, J, J), dtype=torch.float32, device=dev)
+    dq = new(J, B * P)
+    _pgpool_check(B, P, C, J, cn=(x, q, dx, dq), dense=(centers, zn, dz, dA, dcenters, dvariance))
+    if tuple(dz.shape) != (B, C, J) or tuple(dA.shape) != (B, J, J) or dcenters.numel() != C * J or dvariance.numel() != C * J:
+        raise ValueError("dz must be (B, C, J), dA (B, J, J), dcenters / dvariance C * J elements")
+    lib = L.load()
+    st = stream_ptr()
+    dzn, dS, dqs = new(B, C, J), new(B, C, J), new(B, J)
+    check(lib.sar_pgpool_gram_bwd_f32(ptr(zn), ptr(dz), ptr(dA), B, C, J, ptr(dzn), st), "sar_pgpool_gram_bwd_f32")
+    check(lib.sar_pgpool_normalize_bwd_f32(ptr(dzn), ptr(zn), ptr(zp), ptr(n2), ptr(qs), ptr(centers), ptr(tab), B, C, J, ptr(dS),
+                                           ptr(dqs), st), "sar_pgpool_normalize_bwd_f32")
+    check(lib.sar_pgpool_dq_f32(ptr(x), x.stride(0), ptr(dS), ptr(dqs), B, P, C, J, ptr(dq), dq.stride(0), st), "sar_pgpool_dq_f32")
+    check(lib.sar_pgpool_softmax_bwd_f32(ptr(q), q.stride(0), ptr(clamp), B, P, J, ptr(dq), dq.stride(0), st), "sar_pgpool_softmax_bwd_f32")
+    check(lib.sar_pgpool_dx_f32(ptr(x), x.stride(0), ptr(dS), ptr(q), q.stride(0), ptr(dq), dq.stride(0), ptr(tab), B, P, C, J, ptr(dx),
+                                dx.stride(0), st), "sar_pgpool_dx_f32")
+    M0, M1, M2 = dqs, dzn, new(B, C, J)           # (dqs and dzn have been consumed)
+    check(lib.sar_pgpool_rowsum_f32(ptr(dq), dq.stride(0), B, P, J, ptr(M0), st), "sar_pgpool_rowsum_f32")
+    check(lib.sar_pgpool_moment_f32(ptr(x), x.stride(0), ptr(dq), dq.stride(0), B, P, C, J, 0, ptr(M1), st), "sar_pgpool_moment_f32")
+    check(lib.sar_pgpool_moment_f32(ptr(x), x.stride(0), ptr(dq), dq.stride(0), B, P, C, J, 1, ptr(M2), st), "sar_pgpool_moment_f32")
+    check(lib.sar_pgpool_param_grad_f32(ptr(M0), ptr(M1), ptr(M2), ptr(dS), ptr(qs), ptr(zp), ptr(centers), ptr(tab), B, C, J,
+                                        ptr(dcenters), ptr(dvariance), st), "sar_pgpool_param_grad_f32")
+    return dq                                     # (holds dl)
+
+
 # ------------------------------------------------------------------------------------------------ ResNet-18 ops
 def _shape_tag(geo):
     """SAR_PROFILE_SHAPES=1 (diagnostic, tools/pathb_layers.py): one profiler bucket per layer geometry"""
