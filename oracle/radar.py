@@ -138,14 +138,9 @@ def nearest_columns(F_, out_cols):
     return np.minimum(np.floor(j * scale).astype(np.int64), F_ - 1)
 
 
-def spectrogram_torch(x, loc, lam, edges=EDGES, n_fft=256, hop=16, out_cols=0, dtype=None, wcos=None, wsin=None):
-    """Differentiable restatement of the whole layer (layers/virtual_radar.py:93-133) in torch, for the gradients of
-    radar_location / wavelength (autograd of the reference when train_* are set, main_spectrogram.py:133-136).
-    x (B,3,T,V,M) tensor; loc (3,) and lam () tensors (requires_grad as wanted); float64 unless dtype is given.
-    out_cols > 0 applies the nearest column select of models/resnet.py:26.
-    wcos / wsin: (n_fft, n_fft) [k, n] tensors replacing the analytic Fourier kernels -- nnAudio's STFT(trainable=True)
-    holds them as Parameters of shape (n_fft, 1, n_fft) (layers/virtual_radar.py:71-76 train_stft_kernel) and convolves the
-    reflect-padded signal with them; pass leaves with requires_grad to get their gradients."""
+def signal_torch(x, loc, lam, edges=EDGES, dtype=None):
+    """The signal stage of spectrogram_torch on its own (layers/virtual_radar.py:93-123): x (B,3,T,V,M), loc (3,) and lam ()
+    tensors -> (zr, zi), each (B,T), differentiable in loc / lam; float64 unless dtype is given."""
     import torch
     dtype = dtype or torch.float64
     x = torch.as_tensor(x).to(dtype)
@@ -166,7 +161,15 @@ def spectrogram_torch(x, loc, lam, edges=EDGES, n_fft=256, hop=16, out_cols=0, d
     den = st * st * cp * cp + st * st * sp * sp + c * ct * ct
     amp = torch.sqrt(np.pi * c / (den * den))
     psi = 4 * np.pi * dist / lam.to(dtype)
-    zr, zi = (amp * torch.cos(psi)).sum(dim=[2, 3]), (amp * torch.sin(psi)).sum(dim=[2, 3])       # (B,T)
+    return (amp * torch.cos(psi)).sum(dim=[2, 3]), (amp * torch.sin(psi)).sum(dim=[2, 3])       # (B,T)
+
+
+def stft_torch(zr, zi, n_fft=256, hop=16, out_cols=0, dtype=None, wcos=None, wsin=None):
+    """The STFT / log-magnitude / roll / column-select stage of spectrogram_torch on its own (layers/virtual_radar.py:124-133,
+    models/resnet.py:26): zr, zi (B,T) tensors -> (B, n_fft, out_cols or F), differentiable in zr / zi / wcos / wsin."""
+    import torch
+    dtype = dtype or torch.float64
+    zr, zi = torch.as_tensor(zr).to(dtype), torch.as_tensor(zi).to(dtype)
     pad = n_fft // 2
     w = torch.from_numpy(hann_periodic(n_fft)).to(dtype)
     n = torch.arange(n_fft, dtype=dtype)
@@ -186,6 +189,21 @@ def spectrogram_torch(x, loc, lam, edges=EDGES, n_fft=256, hop=16, out_cols=0, d
     if out_cols > 0:
         out = out[:, :, torch.from_numpy(nearest_columns(out.shape[2], out_cols).astype(np.int64))]
     return out
+
+
+def spectrogram_torch(x, loc, lam, edges=EDGES, n_fft=256, hop=16, out_cols=0, dtype=None, wcos=None, wsin=None):
+    """Differentiable restatement of the whole layer (layers/virtual_radar.py:93-133) in torch, for the gradients of
+    radar_location / wavelength (autograd of the reference when train_* are set, main_spectrogram.py:133-136).
+    x (B,3,T,V,M) tensor; loc (3,) and lam () tensors (requires_grad as wanted); float64 unless dtype is given.
+    out_cols > 0 applies the nearest column select of models/resnet.py:26.
+    wcos / wsin: (n_fft, n_fft) [k, n] tensors replacing the analytic Fourier kernels -- nnAudio's STFT(trainable=True)
+    holds them as Parameters of shape (n_fft, 1, n_fft) (layers/virtual_radar.py:71-76 train_stft_kernel) and convolves the
+    reflect-padded signal with them; pass leaves with requires_grad to get their gradients.
+    = stft_torch(signal_torch(...)): the two stages are also callable on their own."""
+    import torch
+    dtype = dtype or torch.float64
+    zr, zi = signal_torch(x, loc, lam, edges, dtype)
+    return stft_torch(zr, zi, n_fft, hop, out_cols, dtype, wcos, wsin)
 
 
 def radar_param_grads(x, weights, loc, lam, **kw):
@@ -208,3 +226,16 @@ def pad_frames(data, num_pad_frames=250, sigma=3):
     T = data.shape[-3]
     f = interp1d(np.linspace(0, 1, T), gaussian_filter1d(data, sigma, axis=-3), 'cubic', axis=-3)
     return f(np.linspace(0, 1, num_pad_frames * T)).astype(f32)
+
+
+def pad_frames_parts(data, num_pad_frames=250, sigma=3):
+    """pad_frames in its two steps: (the Gaussian-smoothed clip in the input's dtype -- gaussian_filter1d keeps it --, the cubic
+    interpolation of that smoothed clip at np.linspace(0, 1, num_pad_frames*T) in float64, NOT yet rounded to float32).
+    pad_frames(data, P, sigma) == pad_frames_parts(data, P, sigma)[1].astype(float32)."""
+    from scipy.interpolate import interp1d
+    from scipy.ndimage import gaussian_filter1d
+    data = np.asarray(data)
+    T = data.shape[-3]
+    sm = gaussian_filter1d(data, sigma, axis=-3)
+    f = interp1d(np.linspace(0, 1, T), sm, 'cubic', axis=-3)
+    return sm, f(np.linspace(0, 1, num_pad_frames * T))

@@ -57,6 +57,15 @@ def test_flat_range():
         w[i] = 0.0
         with pytest.raises(AssertionError, match="overwritten"):
             assert_flat_guards_untouched(w, 10, NAN)
+    # float64 ranges (the spline pieces of the radar up-sampling) and int32 ranges (edge lists): NaN margins compare by bit pattern too
+    for dtype, fill, other in ((torch.float64, NAN, 0.0), (torch.float64, SENTINEL, 1.0), (torch.int32, 1 << 30, 0)):
+        v, w = guarded_flat(10, fill, CPU, dtype=dtype)
+        assert v.data_ptr() % 16 == 0
+        v.fill_(3)
+        assert_flat_guards_untouched(w, 10, fill)
+        w[18 if dtype == torch.int32 else 3] = other
+        with pytest.raises(AssertionError, match="overwritten"):
+            assert_flat_guards_untouched(w, 10, fill)
     with pytest.raises(AssertionError):
         guarded_flat(10, SENTINEL, CPU, k=6)
 

@@ -79,6 +79,8 @@ def _bits(t):
     """the bit patterns of a tensor (a NaN equals itself)"""
     if t.dtype == torch.float32:
         return t.view(torch.int32)
+    if t.dtype == torch.float64:
+        return t.view(torch.int64)
     return t.view(torch.int16) if t.dtype == torch.bfloat16 else t
 
 
