@@ -804,6 +804,50 @@ int sar_pgpool_param_grad_f32(const float* M0, const float* M1, const float* M2,
                               sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * GPool(keeprate), the top-k graph pooling of models/stgcn_debug.py:29-72, fp32 (csrc/gpool.hip).  x (N, C, T, V), A (N, K, V, V)
+ * contiguous, 1 <= V <= SAR_GPOOL_VMAX, 1 <= K <= SAR_GPOOL_KMAX, 1 <= keep <= V, N <= 65535, N*C*T*V < 2^31: anything else is
+ * SAR_E_ARG / SAR_E_UNSUP before a launch.
+ * A strided tensor is passed as (pointer, s_n, s_c): element (n, c, t, w) at n*s_n + c*s_c + t*W + w (W = V for x and dx, keep for
+ * out and dout) -- NCHW: s_n = C*T*W, s_c = T*W; a CN matrix [C][ld]: s_n = T*W, s_c = ld.  The runs of T*W floats may not overlap.
+ * part / dspart: [N][sar_gpool_groups(C, T)][V | keep] partial sums; idx (N, keep) int32; pos (N, V) int32 (i where v = idx[n][i],
+ * else -1); sv = sigmoid(y[idx]) (N, keep); y, dy (N, V); ph (C*T) = p / max(|p|, 1e-6); norm = {sum p^2, 1 / max(|p|, 1e-6)};
+ * dphp (N, C*T) and dph (C*T) are scratch.  No atomics: repeated launches are bitwise equal, and everything but dp depends on the
+ * sample's own data only.
+ *   sar_gpool_prep_f32     ph, norm from p
+ *   sar_gpool_score_f32    part: y[n, v] = sum_{c,t} x[n, c, t, v] ph[c*T + t] over each group of channels
+ *   sar_gpool_select_f32   y (the groups in order, fp64), idx = the keep best of y[n] (descending, ties in ascending v, NaN last), sv, pos
+ *   sar_gpool_gather_f32   out[n, c, t, i] = x[n, c, t, idx[n, i]] sv[n, i]
+ *   sar_gpool_adj_f32      A_out[n, k, i, j] = sum_u A[n, k, idx_i, u] A[n, k, u, idx_j]
+ *   sar_gpool_adj_bwd_f32  dA[n, k] = G A^T + A^T G, G = dA_out scattered to rows idx_i, columns idx_j (every element written)
+ *   sar_gpool_ds_f32       dspart: sum_{c,t} dout[n, c, t, i] x[n, c, t, idx_i] over each group of channels
+ *   sar_gpool_dy_f32       dy[n, idx_i] = ds sv (1 - sv), 0 elsewhere
+ *   sar_gpool_dx_f32       dx[n, c, t, v] = (v = idx_i ? dout[n, c, t, i] sv[n, i] : 0) + dy[n, v] ph[c*T + t] (every element written;
+ *                          dx may not be x); dphp[n][ct] = sum_i dy[n, idx_i] x[n, ct, idx_i]
+ *   sar_gpool_dp_f32       dph = sum_n dphp[n] (sample order, fp64); dp = (dph - ph <dph, ph>) norm[1], dph norm[1] where
+ *                          norm[0] <= 1e-12 */
+#define SAR_GPOOL_VMAX 64
+#define SAR_GPOOL_KMAX 8
+int sar_gpool_groups(int C, int T);
+int sar_gpool_prep_f32(const float* p, int CT, float* ph, float* norm, sar_stream_t s);
+int sar_gpool_score_f32(const float* x, int64_t s_n, int64_t s_c, const float* ph, int N, int C, int T, int V, float* part,
+                        sar_stream_t s);
+int sar_gpool_select_f32(const float* part, int N, int C, int T, int V, int keep, float* y, int32_t* idx, float* sv, int32_t* pos,
+                         sar_stream_t s);
+int sar_gpool_gather_f32(const float* x, int64_t s_n, int64_t s_c, const int32_t* idx, const float* sv, int N, int C, int T, int V,
+                         int keep, float* out, int64_t o_sn, int64_t o_sc, sar_stream_t s);
+int sar_gpool_adj_f32(const float* A, const int32_t* idx, int N, int K, int V, int keep, float* A_out, sar_stream_t s);
+int sar_gpool_adj_bwd_f32(const float* A, const float* dA_out, const int32_t* idx, const int32_t* pos, int N, int K, int V, int keep,
+                          float* dA, sar_stream_t s);
+int sar_gpool_ds_f32(const float* x, int64_t s_n, int64_t s_c, const float* dout, int64_t d_sn, int64_t d_sc, const int32_t* idx, int N,
+                     int C, int T, int V, int keep, float* part, sar_stream_t s);
+int sar_gpool_dy_f32(const float* part, const float* sv, const int32_t* idx, int N, int C, int T, int V, int keep, float* dy,
+                     sar_stream_t s);
+int sar_gpool_dx_f32(const float* x, int64_t s_n, int64_t s_c, const float* dout, int64_t d_sn, int64_t d_sc, const int32_t* pos,
+                     const float* sv, const float* dy, const float* ph, int N, int C, int T, int V, int keep, float* dx, int64_t g_sn,
+                     int64_t g_sc, float* dphp, sar_stream_t s);
+int sar_gpool_dp_f32(const float* dphp, const float* ph, const float* norm, int N, int CT, float* dph, float* dp, sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * bf16 configuration (bf16 activations in HBM, bf16 MFMA operands, fp32 accumulation, fp32
  * BatchNorm statistics, fp32 master weights).
  *

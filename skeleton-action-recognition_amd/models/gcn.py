@@ -135,23 +135,26 @@ DENSE_CONTRACTION = (ops.graph_dense_fwd, ops.graph_dense_bwd_data, ops.graph_de
 
 class _ConvContractFn(torch.autograd.Function):
     """the 1x1 convolution, then `contraction` with A: GraphConv (SAMPLE_CONTRACTION), the dense path of GraphConvTD and AdjGraphConv
-    (DENSE_CONTRACTION, dA included).  F = the channels that leave the contraction, geo = the column geometry of the product"""
+    (DENSE_CONTRACTION, dA included).  F = the channels that leave the contraction, geo = the column geometry of the product,
+    columns = (NCHW -> CN, CN -> NCHW of a given shape): a layer whose contraction wants another column order brings its own pair"""
 
     @staticmethod
-    def forward(ctx, x, A, kernel, bias, contraction, dims, F, geo):
+    def forward(ctx, x, A, kernel, bias, contraction, dims, F, geo, columns=(to_cn, from_cn)):
         C = x.shape[1]
+        to_cn, from_cn = columns
         X = to_cn(x)
         y = _conv1x1_fwd(X, kernel.view(C, -1), bias, geo)
         out = torch.empty((F, X.shape[1]), dtype=torch.float32, device=x.device)
         contraction[0](y, A, out, *dims)
         ctx.save_for_backward(X, y, A, kernel)
-        ctx.contraction, ctx.dims, ctx.geo, ctx.shape = contraction, dims, geo, tuple(x.shape)
+        ctx.contraction, ctx.dims, ctx.geo, ctx.shape, ctx.columns = contraction, dims, geo, tuple(x.shape), columns
         return from_cn(out, (x.shape[0], F) + tuple(x.shape[2:]))
 
     @staticmethod
     def backward(ctx, dout):
         X, y, A, kernel = ctx.saved_tensors
         _, bwd_data, adjacency_grad = ctx.contraction
+        to_cn, from_cn = ctx.columns
         C = ctx.shape[1]
         need_x, need_A, need_k, need_b = ctx.needs_input_grad[:4]
         dc = to_cn(dout.contiguous())
@@ -168,7 +171,7 @@ class _ConvContractFn(torch.autograd.Function):
                 dW = dW.view(kernel.shape)
             if need_x:
                 dx = from_cn(_conv1x1_dgrad(dy, W, ctx.geo), ctx.shape)
-        return dx, dA, dW, db, None, None, None, None
+        return dx, dA, dW, db, None, None, None, None, None
 
 
 class _GraphConvTDFusedFn(torch.autograd.Function):

@@ -189,6 +189,18 @@ SIGNATURES = {
     "sar_pgpool_softmax_bwd_f32": (_i, [_fp, _i64, _fp, _i, _i64, _i, _fp, _i64, _fp]),
     "sar_pgpool_dx_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _fp, _i64, _fp, _i, _i64, _i, _i, _fp, _i64, _fp]),
     "sar_pgpool_param_grad_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
+    # GPool top-k graph pooling (csrc/gpool.hip)
+    "sar_gpool_groups": (_i, [_i, _i]),
+    "sar_gpool_prep_f32": (_i, [_fp, _i, _fp, _fp, _fp]),
+    "sar_gpool_score_f32": (_i, [_fp, _i64, _i64, _fp, _i, _i, _i, _i, _fp, _fp]),
+    "sar_gpool_select_f32": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
+    "sar_gpool_gather_f32": (_i, [_fp, _i64, _i64, _fp, _fp, _i, _i, _i, _i, _i, _fp, _i64, _i64, _fp]),
+    "sar_gpool_adj_f32": (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp]),
+    "sar_gpool_adj_bwd_f32": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp]),
+    "sar_gpool_ds_f32": (_i, [_fp, _i64, _i64, _fp, _i64, _i64, _fp, _i, _i, _i, _i, _i, _fp, _fp]),
+    "sar_gpool_dy_f32": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp]),
+    "sar_gpool_dx_f32": (_i, [_fp, _i64, _i64, _fp, _i64, _i64, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _i64, _i64, _fp, _fp]),
+    "sar_gpool_dp_f32": (_i, [_fp, _fp, _fp, _i, _i, _fp, _fp, _fp]),
     "sar_graph_dense_nparts": (_i, [_i64]),
     "sar_graph_dense_fwd_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _i64, _fp, _fp, _i64, _fp]),
     "sar_graph_dense_bwd_data_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _i, _i, _i, _i64, _fp]),

@@ -1097,6 +1097,139 @@ def pgpool_backward(x, B, P, centers, zn, saved, dz, dA, dx, dcenters, dvariance
     return dq                                     # (holds dl)
 
 
+# ------------------------------------------------------------------------------------------------ GPool top-k graph pooling
+# csrc/gpool.hip (include/sar_hip.h: GPool).  x / out / their gradients are 4-D (N, C, T, W) tensors OR VIEWS whose two inner strides
+# are (W, 1): the NCHW tensors of the modules, or the view X[:, :N*T*W].view(C, N, T, W).permute(1, 0, 2, 3) of an engine's CN matrix
+GPOOL_VMAX, GPOOL_KMAX, GPOOL_NMAX = 64, 8, 65535
+
+
+def gpool_keep(keeprate, V):
+    """int(float32(keeprate) * float32(V)), the reference's `int(keeprate * tf.cast(V, float32))`"""
+    import numpy as np
+    keep = int(np.float32(keeprate) * np.float32(V))
+    if not (0.0 < float(keeprate) <= 1.0) or keep < 1:
+        raise ValueError("keeprate must be in (0, 1] and keep at least one of the V = %d vertices (got keeprate = %r: keep = %d)"
+                         % (V, keeprate, keep))
+    return keep
+
+
+def _gpool_view(t, shape, what):
+    if not (isinstance(t, torch.Tensor) and t.dim() == 4 and tuple(t.shape) == tuple(shape)):
+        raise ValueError("%s must be a 4-D tensor of shape %s (got %s)" % (what, tuple(shape), tuple(t.shape) if hasattr(t, "shape") else t))
+    N, C, T, W = shape
+    sn, sc = t.stride(0), t.stride(1)
+    inner = (T == 1 or t.stride(2) == W) and (W == 1 or t.stride(3) == 1)
+    nchw = sc >= T * W and (C == 1 or N == 1 or sn >= C * sc)
+    cn = sn >= T * W and (N == 1 or C == 1 or sc >= N * sn)
+    if not (inner and (nchw or cn)):
+        raise ValueError("%s must have unit inner strides (W, 1) and be channel-major per sample (NCHW) or sample-major per channel (a CN "
+                         "matrix): got shape %s, strides %s" % (what, tuple(t.shape), tuple(t.stride())))
+    return sn, sc
+
+
+def _gpool_dense(t, shape, what):
+    if not (isinstance(t, torch.Tensor) and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous tensor of shape %s (got %s)" % (what, tuple(shape), tuple(t.shape) if hasattr(t, "shape") else t))
+
+
+def _gpool_device(f32=(), i32=()):
+    """after the shapes and strides: everything is on the GPU in its dtype"""
+    for ts, dtype in ((f32, torch.float32), (i32, torch.int32)):
+        for t in ts:
+            if not (t.is_cuda and t.dtype == dtype):
+                raise ValueError("GPool operands must be %s CUDA tensors (got %s on %s)" % (dtype, t.dtype, t.device))
+
+
+def _gpool_check(N, C, T, V, K):
+    if not (1 <= V <= GPOOL_VMAX and 1 <= K <= GPOOL_KMAX):
+        raise ValueError("GPool is built for 1 <= V <= %d and 1 <= K <= %d (got V = %d, K = %d)" % (GPOOL_VMAX, GPOOL_KMAX, V, K))
+    if not (1 <= N <= GPOOL_NMAX and C >= 1 and T >= 1 and N * C * T * V < 1 << 31):
+        raise ValueError("GPool is built for 1 <= N <= %d and fewer than 2^31 elements (got N = %d, C = %d, T = %d, V = %d)"
+                         % (GPOOL_NMAX, N, C, T, V))
+
+
+def gpool_forward(x, A, p, keeprate, out=None):
+    """GPool forward (models/stgcn_debug.py:39-72) of x (N, C, T, V) -- a tensor or a strided view, see above --, A (N, K, V, V) and
+    projection_vector p (C T elements).  Returns (out (N, C, T, keep), A_out (N, K, keep, keep), saved); `out` may be given as a view
+    of the caller's buffer.  saved = (idx (N, keep) int32, pos (N, V) int32, y (N, V), s (N, keep), ph (C T), norm (2)) is what
+    gpool_backward needs besides x, A and p."""
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
+        raise ValueError("x must be 4-D (N, C, T, V)")
+    if not (isinstance(A, torch.Tensor) and A.dim() == 4):
+        raise ValueError("A must be 4-D (N, K, V, V): expand a 3-D adjacency to (N, K, V, V)")
+    N, C, T, V = x.shape
+    K = A.shape[1]
+    _gpool_check(N, C, T, V, K)
+    keep = gpool_keep(keeprate, V)
+    sn, sc = _gpool_view(x, (N, C, T, V), "x")
+    _gpool_dense(A, (N, K, V, V), "A")
+    if not (isinstance(p, torch.Tensor) and p.numel() == C * T):
+        raise ValueError("projection_vector must hold C * T = %d elements" % (C * T))
+    _gpool_dense(p, tuple(p.shape), "projection_vector")
+    _gpool_device((x, A, p))
+    dev = x.device
+    if out is None:
+        out = torch.empty((N, C, T, keep), dtype=torch.float32, device=dev)
+    on, oc = _gpool_view(out, (N, C, T, keep), "out")
+    _gpool_device((out,))
+    lib = L.load()
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    newi = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    ph, norm, part = new(C * T), new(2), new(N, lib.sar_gpool_groups(C, T), V)
+    y, s, idx, pos, A_out = new(N, V), new(N, keep), newi(N, keep), newi(N, V), new(N, K, keep, keep)
+    st = stream_ptr()
+    check(lib.sar_gpool_prep_f32(ptr(p), C * T, ptr(ph), ptr(norm), st), "sar_gpool_prep_f32")
+    check(lib.sar_gpool_score_f32(ptr(x), sn, sc, ptr(ph), N, C, T, V, ptr(part), st), "sar_gpool_score_f32")
+    check(lib.sar_gpool_select_f32(ptr(part), N, C, T, V, keep, ptr(y), ptr(idx), ptr(s), ptr(pos), st), "sar_gpool_select_f32")
+    check(lib.sar_gpool_gather_f32(ptr(x), sn, sc, ptr(idx), ptr(s), N, C, T, V, keep, ptr(out), on, oc, st), "sar_gpool_gather_f32")
+    check(lib.sar_gpool_adj_f32(ptr(A), ptr(idx), N, K, V, keep, ptr(A_out), st), "sar_gpool_adj_f32")
+    return out, A_out, (idx, pos, y, s, ph, norm)
+
+
+def gpool_backward(x, A, saved, dout, dA_out, dx=None):
+    """Backward of gpool_forward from dout (N, C, T, keep; tensor or strided view) and dA_out (N, K, keep, keep); either may be None.
+    Returns (dx, dp (C T), dA): dx / dp are None without dout, dA is None without dA_out.  dx may be given as a view of the caller's
+    buffer; every element of it is written."""
+    idx, pos, y, s, ph, norm = saved
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4 and isinstance(A, torch.Tensor) and A.dim() == 4):
+        raise ValueError("x must be 4-D (N, C, T, V) and A 4-D (N, K, V, V)")
+    N, C, T, V = x.shape
+    K, keep = A.shape[1], idx.shape[1]
+    _gpool_check(N, C, T, V, K)
+    sn, sc = _gpool_view(x, (N, C, T, V), "x")
+    _gpool_dense(A, (N, K, V, V), "A")
+    _gpool_dense(idx, (N, keep), "idx")
+    _gpool_dense(pos, (N, V), "pos")
+    dev = x.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    dp = dA = None
+    if dout is not None:
+        dn, dc = _gpool_view(dout, (N, C, T, keep), "dout")
+        if dx is not None:
+            gn, gc = _gpool_view(dx, (N, C, T, V), "dx")
+    if dA_out is not None:
+        _gpool_dense(dA_out, (N, K, keep, keep), "dA_out")
+    _gpool_device((x, A, y, s, ph, norm) + tuple(t for t in (dout, dA_out, dx) if t is not None), (idx, pos))
+    if dout is not None and dx is None:
+        dx = new(N, C, T, V)
+        gn, gc = _gpool_view(dx, (N, C, T, V), "dx")
+    lib = L.load()
+    st = stream_ptr()
+    if dout is not None:
+        part, dy, dphp, dph, dp = new(N, lib.sar_gpool_groups(C, T), keep), new(N, V), new(N, C * T), new(C * T), new(C * T)
+        check(lib.sar_gpool_ds_f32(ptr(x), sn, sc, ptr(dout), dn, dc, ptr(idx), N, C, T, V, keep, ptr(part), st), "sar_gpool_ds_f32")
+        check(lib.sar_gpool_dy_f32(ptr(part), ptr(s), ptr(idx), N, C, T, V, keep, ptr(dy), st), "sar_gpool_dy_f32")
+        check(lib.sar_gpool_dx_f32(ptr(x), sn, sc, ptr(dout), dn, dc, ptr(pos), ptr(s), ptr(dy), ptr(ph), N, C, T, V, keep, ptr(dx), gn, gc,
+                                   ptr(dphp), st), "sar_gpool_dx_f32")
+        check(lib.sar_gpool_dp_f32(ptr(dphp), ptr(ph), ptr(norm), N, C * T, ptr(dph), ptr(dp), st), "sar_gpool_dp_f32")
+    else:
+        dx = None
+    if dA_out is not None:
+        dA = new(N, K, V, V)
+        check(lib.sar_gpool_adj_bwd_f32(ptr(A), ptr(dA_out), ptr(idx), ptr(pos), N, K, V, keep, ptr(dA), st), "sar_gpool_adj_bwd_f32")
+    return dx, dp, dA
+
+
 # ------------------------------------------------------------------------------------------------ ResNet-18 ops
 def _shape_tag(geo):
     """SAR_PROFILE_SHAPES=1 (diagnostic, tools/pathb_layers.py): one profiler bucket per layer geometry"""
