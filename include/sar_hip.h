@@ -930,6 +930,23 @@ int sar_cn8_to_cn(const void* x, int64_t ld_x, float* out, int64_t ld_out, int C
 int sar_pre_normalize_f32(const float* x, float* out, int N, int T, int V, int M, int z0, int z1, int x0, int x1, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * Training-time augmentation of skeleton clips (csrc/augment.hip; sar_amd/augment.py draws the parameters).  x, out:
+ * (N, 3, T, V, M) fp32, C-contiguous, NOT overlapping (frames are gathered); params: (N, 16) fp32 on the device, one row
+ *   [p, o, alpha0, beta0, gamma0, s0, dx0, dy0, dz0, alpha1, beta1, gamma1, s1, dx1, dy1, dz1]
+ * per clip.  Per clip: L = one past the last frame with a non-zero coordinate (L = 0: the output clip is zero); the window of
+ * Lc = max(1, floor(p L)) frames from b = min(floor(o (L - Lc + 1)), L - Lc) is resized to T frames, linear with half-pixel
+ * centres (torch interpolate(mode='linear', align_corners=False)); a joint that is null (all coordinates exactly zero) in the
+ * nearer source frame stays null, one that is null in the farther frame only is not blended.  Output frame t then gets
+ * out = s (R u) + d with every parameter at tau = t / (T - 1) between its two key values and R = Rz(gamma) Ry(beta) Rx(alpha)
+ * about the origin, built in double and rounded to fp32.  crop == 0: L := T, p := 1, o := 0 (identity time map, padding kept).
+ * Identity parameters on a clip without trailing null frames give out bitwise equal to x.  The kernel is a pure function of its
+ * arguments: one workgroup per clip, no atomics, no workspace; repeated launches are bitwise equal.  Lc and b are clamped into
+ * the clip, so no parameter row reads outside x.  Built for V <= 32, M <= 4, T <= 2048 (SAR_E_UNSUP otherwise); overlapping
+ * buffers: SAR_E_ARG.  Nothing is launched on an error.
+ * ------------------------------------------------------------------------------------------------ */
+int sar_augment_clips_f32(const float* x, const float* params, float* out, int N, int T, int V, int M, int crop, sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * TemporalSampler (models/lstm_sampler.py:1-27): a stack of Keras LSTM layers scores every frame, the top_k best frames are
  * gathered and scaled by their scores.  csrc/lstm.hip, fp32.  The stack's activations are CN matrices [rows][ld] with TIME-MAJOR
  * columns t*N + n (sequence n, step t): every ld >= T*N, no alignment beyond the element, columns past T*N are neither read nor

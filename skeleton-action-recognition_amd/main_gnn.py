@@ -68,6 +68,13 @@ def get_parser():
                         help="apply data_gen/preprocess.py `pre_normalization` (pad null frames, centre on the spine, hip->spine onto z, "
                              "shoulders onto x) to every training and test batch on the device (csrc/prenorm.hip): for raw clips that "
                              "did not go through data_gen/gen_joint_data.py; bone / motion streams are taken from the normalised joints")
+    parser.add_argument('--augment', default='', metavar='SPEC',
+                        help="augment every TRAINING batch on the device (csrc/augment.hip), after --pre-normalize and before the step: "
+                             "'rot=0.3,scale=0.1,shift=0.1,crop=0.5,move=1' = rotation up to 0.3 rad per axis, scale in [0.9, 1.1], shift up "
+                             "to 0.1 per axis, a temporal crop of 50-100 %% of the valid frames resized to T, parameters moving linearly "
+                             "over the clip (move=0: constant); test batches are never touched (sar_amd/augment.py)")
+    parser.add_argument('--augment-seed', type=int, default=0,
+                        help='key of the augmentation draws: the table of a step depends on (seed, epoch, iteration, rank) alone')
     parser.add_argument('--verify-crc', default='full', choices=['full', 'length', 'off'],
                         help="TFRecord shards: 'full' checks the masked CRC-32C of every length field and payload (what tf.data's "
                              "reader does), 'length' the length fields only, 'off' the framing only")
@@ -103,7 +110,7 @@ def main():
     run_params = {k: v for k, v in vars(arg).items()
                   if k not in ("train_data_path", "test_data_path", "log_dir", "save_freq", "freeze_graph_until", "gpus", "resume",
                                "save_scores", "verify_crc") and not (k == "mfma" and v == "fp32")
-                  and not (k in ("trainable_adjacency", "pre_normalize") and not v)}
+                  and not (k in ("trainable_adjacency", "pre_normalize", "augment", "augment_seed") and not v)}
     run_name = str(run_params).replace(" ", "").replace("'", "").replace(",", "-")[1:-1]
     if arg.notes:
         run_name += "-" + arg.notes
@@ -135,6 +142,10 @@ def main():
                             trainable_adjacency=arg.trainable_adjacency)
     eng = model.engine
     trainer = Trainer(eng, batch_size=arg.batch_size, base_lr=arg.base_lr, steps=arg.steps, world_size=world)
+    augment = None
+    if arg.augment:
+        from sar_amd.augment import ClipAugment
+        augment = ClipAugment.parse(arg.augment, seed=arg.augment_seed)
     log = open(os.path.join(arg.log_dir, "scalars.jsonl"), "a") if rank == 0 else None
 
     def scalar(tag, value, step):
@@ -172,7 +183,10 @@ def main():
             next_iter = train_data.batches(arg.batch_size, rank, world, dev, shuffle=True, epoch=epoch)
         train_iter_obj, next_iter = next_iter, None
         for it, (x, y) in enumerate(train_iter_obj):
-            logits, loss = trainer.step(ops.pre_normalize(x) if arg.pre_normalize else x, y)
+            xin = ops.pre_normalize(x) if arg.pre_normalize else x
+            if augment is not None:
+                xin = augment(xin, epoch, it, rank)
+            logits, loss = trainer.step(xin, y)
             if trace_dir:
                 trace["ids"].append([epoch, x[:, 0, 0, 0, 0].tolist()])
             pending.append(torch.stack([loss.reshape(()) * 1.0, topk_correct(logits, y, 1).float() / global_batch_size,

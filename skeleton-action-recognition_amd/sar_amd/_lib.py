@@ -239,6 +239,8 @@ SIGNATURES = {
     "sar_cn8_to_cn": (_i, [_fp, _i64, _fp, _i64, _i, _i64, _fp]),
     # pre-normalisation of raw clips (csrc/prenorm.hip)
     "sar_pre_normalize_f32": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _fp]),
+    # training-time augmentation of clips (csrc/augment.hip)
+    "sar_augment_clips_f32": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _fp]),
     # TemporalSampler: LSTM recurrence, top-k, frame gather (csrc/lstm.hip)
     "sar_lstm_fwd_f32": (_i, [_fp, _i64, _fp, _fp, _i64, _fp, _i64, _fp, _i64, _i, _i, _i, _fp]),
     "sar_lstm_bwd_f32": (_i, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _i64, _i, _i, _i, _fp]),

@@ -701,6 +701,40 @@ def pre_normalize(x, out=None, zaxis=(0, 1), xaxis=(8, 4)):
     return out
 
 
+AUGMENT_MAX_T, AUGMENT_MAX_V, AUGMENT_MAX_M = 2048, 32, 4      # csrc/augment.hip AG_MAX_*
+
+
+def augment_clips(x, params, crop=False, out=None):
+    """Training-time augmentation of a batch of clips (N, 3, T, V, M) on the device (csrc/augment.hip): per clip a temporal
+    crop-resize (only with `crop`), then a per-frame rotation, scale and shift between two key frames.  `params` is the (N, 16)
+    float32 table of sar_amd.augment.ClipAugment.table on x's device.  Returns `out` (a new tensor when None); `out` must not
+    overlap x.  Every argument error is raised before the library is touched."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()):
+        raise L.SarError("augment_clips: x must be a contiguous cuda float32 tensor")
+    if x.dim() != 5 or x.shape[1] != 3:
+        raise L.SarError("augment_clips: need (N, 3, T, V, M) coordinates, got %s" % (tuple(x.shape),))
+    N, _, T, V, M = x.shape
+    if not (torch.is_tensor(params) and params.dtype == torch.float32 and params.device == x.device and params.is_contiguous()
+            and tuple(params.shape) == (N, 16)):
+        raise L.SarError("augment_clips: params must be a contiguous (%d, 16) float32 tensor on %s" % (N, x.device))
+    if T < 1 or V < 1 or M < 1 or T > AUGMENT_MAX_T or V > AUGMENT_MAX_V or M > AUGMENT_MAX_M:
+        raise L.SarError("augment_clips: built for 1 <= T <= %d, V <= %d, M <= %d (got T %d V %d M %d)"
+                         % (AUGMENT_MAX_T, AUGMENT_MAX_V, AUGMENT_MAX_M, T, V, M))
+    if out is None:
+        out = torch.empty_like(x)
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device):
+        raise L.SarError("augment_clips: out must be a contiguous cuda float32 tensor on x's device")
+    if out.shape != x.shape:
+        raise L.SarError("augment_clips: out %s does not match x %s" % (tuple(out.shape), tuple(x.shape)))
+    nbytes = x.numel() * 4
+    for name, other, nb in (("x", x, nbytes), ("params", params, params.numel() * 4)):
+        if nbytes and nb and out.data_ptr() < other.data_ptr() + nb and other.data_ptr() < out.data_ptr() + nbytes:
+            raise L.SarError("augment_clips: out must not overlap %s" % name)
+    check(L.load().sar_augment_clips_f32(ptr(x), ptr(params), ptr(out), N, T, V, M, int(bool(crop)), stream_ptr()),
+          "sar_augment_clips_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ dense adjacency
 def graph_dense_fwd(y, A, out, K, F, V, nframes, stats=False, add=None):
     """out[m] = sum_k y[k F + m] . A_k (+ add[m]) (sar_graph_dense_fwd_f32); returns (partials, nparts) when stats."""
