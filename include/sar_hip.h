@@ -571,9 +571,10 @@ int sar_bn_relu_maxpool_bwd_nparts(int B, int H, int W);   /* partial sums per c
 int sar_bn_relu_maxpool_bwd_f32(const float* x, const float* scale, const float* shift, const float* mean,
                                 const float* dy, float* dz, float* partials, int nparts, int C, int B, int H, int W,
                                 int64_t ld_x, int64_t ld_y, sar_stream_t s);
-/* torch.optim.Adam (main_spectrogram.py:106) over flat buffers; step_dev[0] = t (>= 1), lr_dev[0] = lr. */
+/* torch.optim.Adam (main_spectrogram.py:106) over flat buffers; step_dev[0] = t (>= 1), lr_dev[0] = lr.  The betas are doubles:
+ * 1 - beta and 1 - beta^t are formed in double, as torch forms them, and rounded to float32 once. */
 int sar_adam_f32(float* w, float* m, float* v, const float* g, int64_t n, const float* lr_dev, const float* step_dev,
-                 float beta1, float beta2, float eps, sar_stream_t s);
+                 double beta1, double beta2, float eps, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense (trainable) adjacency, SURVEY.md 8(f)-4: the contraction of models/gcn.py:207-208 / 236-237 (AdjGraphConv) with

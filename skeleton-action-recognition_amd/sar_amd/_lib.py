@@ -140,7 +140,7 @@ SIGNATURES = {
     "sar_bn_relu_maxpool_fwd_f32": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i64, _i64, _fp]),
     "sar_bn_relu_maxpool_bwd_nparts": (_i, [_i, _i, _i]),
     "sar_bn_relu_maxpool_bwd_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i64, _i64, _fp]),
-    "sar_adam_f32": (_i, [_fp, _fp, _fp, _fp, _i64, _fp, _fp, _f, _f, _f, _fp]),
+    "sar_adam_f32": (_i, [_fp, _fp, _fp, _fp, _i64, _fp, _fp, _d, _d, _f, _fp]),
     "sar_vr_signal_f32": (_i, [_fp, _i, _i, _i, _i, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp]),
     "sar_stft_logmag_f32": (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _i, _fp, _fp]),
     "sar_stft_logmag_bwd_workspace_floats": (_i64, [_i, _i, _i, _i]),

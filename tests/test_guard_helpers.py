@@ -245,3 +245,47 @@ def test_launch_record_on_the_cpu():
         g.check_nothing_written()
     slabs = g.slab_batch(_cpu_reduce)
     assert g.slabs == [slabs]
+
+
+# ---- kept inputs, int64 label ranges, in-place buffers and outputs whose specified result is NaN (tests/test_gpu_head_edges.py)
+
+def test_kept_inputs_and_label_ranges_on_the_cpu():
+    class Kept(Launch):
+        KEEP_INPUTS = True
+    g = Kept(CPU, 7)
+    x = g.inp(torch.ones(C, N))
+    labels = g.flat_in(torch.arange(6, dtype=torch.int64).view(2, 3), fill=1 << 40)
+    name, whole, copy = g.ins[1]
+    assert len(g.ins) == 2 and labels.dtype == torch.int64 and labels.shape == (2, 3) and labels.data_ptr() % 16 == 0
+    assert whole.numel() == 6 + 16 and bool((whole[:8] == 1 << 40).all()) and bool((whole[-8:] == 1 << 40).all())
+    assert torch.equal(labels.reshape(-1), torch.arange(6)) and copy.data_ptr() != whole.data_ptr()
+    cell = g.flat_in(torch.tensor([0.1]))
+    assert cell.shape == (1,) and bool(torch.isnan(g.ins[2][1][:8]).all())
+    g.check()
+    for t, where in ((labels, (1, 2)), (x, (0, 0)), (g.ins[1][1], 3), (g.ins[0][1], (0, 0))):   # a live element, a margin: each is seen
+        old = t[where].clone()
+        t[where] = 77
+        with pytest.raises(AssertionError, match="of an input's allocation were modified"):
+            g.check()
+        t[where] = old
+        g.check()
+    assert not Launch(CPU, 0).ins and Launch(CPU, 0).inp(torch.ones(C, N)).shape == (C, N) and not Launch.KEEP_INPUTS
+
+
+def test_in_place_buffers_and_nan_results_on_the_cpu():
+    g = Launch(CPU, 0)
+    w = g.flat("w", torch.arange(5, dtype=torch.float32))
+    assert torch.equal(w, torch.arange(5.0)) and bool((g.flats["w"][1][:8] == SENTINEL).all())
+    loss = g.flat("loss", 1)
+    loss[0] = NAN
+    with pytest.raises(AssertionError, match="loss .pad 0.: not finite"):
+        g.check()
+    g.nan_ok = {"loss"}
+    g.check()
+    w[4] = float("inf")                                  # the exemption is by name
+    with pytest.raises(AssertionError, match="w .pad 0.: not finite"):
+        g.check()
+    w[4] = 4.0
+    g.flats["loss"][1][0] = 0.0                          # and does not cover the guards
+    with pytest.raises(AssertionError, match="overwritten"):
+        g.check()

@@ -148,13 +148,32 @@ class Launch:
     FRONT, BACK, KFLAT = 4, 2, 8      # guard rows of every operand, guard elements of a flat range
     IN_BACK = 2                       # guard rows behind an INPUT (a family whose stagers round the channel count up asks for more)
 
+    KEEP_INPUTS = False               # keep a copy of every input's allocation: check() then asserts that no launch modified one
+
     def __init__(self, dev, pad):
         self.dev, self.pad = dev, pad
         self.outs, self.flats, self.masks, self.parts, self.refs, self.slabs = {}, {}, {}, {}, [], []
+        self.ins, self.nan_ok = [], set()     # (name, allocation, its copy) of the kept inputs; outputs whose specified result holds NaN
 
     def inp(self, src):
         """a (C, n) input as a guarded view, NaN all around"""
-        return guarded(src.float(), self.pad, NAN, self.dev, self.FRONT, self.IN_BACK)[0]
+        view, whole = guarded(src.float(), self.pad, NAN, self.dev, self.FRONT, self.IN_BACK)
+        if self.KEEP_INPUTS:
+            self.ins.append(("input %d" % len(self.ins), whole, whole.clone()))
+        return view
+
+    def flat_in(self, src, fill=NAN):
+        """a flat input of src's dtype and shape between KFLAT elements of `fill` (an int64 label range takes a label no class has),
+        kept: check() asserts that the live elements and both margins are what they were"""
+        view, whole = guarded_flat(src, fill, self.dev, self.KFLAT, dtype=src.dtype)
+        self.ins.append(("input %d" % len(self.ins), whole, whole.clone()))
+        return view.view(src.shape)
+
+    def check_inputs(self):
+        for name, whole, copy in self.ins:
+            bad = _bits(whole) != _bits(copy)
+            assert not bool(bad.any()), "%s (pad %d): %d element(s) of an input's allocation were modified, the first at flat index %d" \
+                % (name, self.pad, int(bad.sum()), int(bad.reshape(-1).nonzero()[0]))
 
     def out(self, name, C, n):
         view, whole = guarded((C, n), self.pad, SENTINEL, self.dev, self.FRONT, self.BACK)
@@ -162,6 +181,7 @@ class Launch:
         return view
 
     def flat(self, name, n):
+        """a flat output of n elements, or an in-place buffer when a tensor is given (the live elements then start as its values)"""
         view, whole = guarded_flat(n, SENTINEL, self.dev, self.KFLAT)
         self.flats[name] = (view, whole)
         return view
@@ -193,8 +213,9 @@ class Launch:
 
     def check(self):
         self.check_guards()                                                                      # 3
+        self.check_inputs()
         for name, (view, _) in list(self.outs.items()) + list(self.flats.items()):                # 4
-            assert bool(torch.isfinite(view).all()), "%s (pad %d): not finite" % (name, self.pad)
+            assert name in self.nan_ok or bool(torch.isfinite(view).all()), "%s (pad %d): not finite" % (name, self.pad)
         for name, t in self.parts.items():
             assert bool(torch.isfinite(t).all()), "partials %s (pad %d): not finite" % (name, self.pad)
         for s in self.slabs:
