@@ -319,34 +319,30 @@ int sar_data_bn_bwd_reduce_f32(const float* x, int N, int C, int T, int V, int M
                                const float* dy, int64_t ld_dy, const float* mean, float* partials, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
- * Block tail, models/stgcn.py:37,62-63:  y = relu(u*sc[c]+sh[c] + res)
- *   res_kind 0: none ; 1: identity (res = r) ; 2: conv residual (res = r*rsc[c]+rsh[c])
+ * Block tail, models/stgcn.py:37,62-63 and models/resnet18.py:46-63, and its gradient: one entry point per pass.  An optional
+ * pointer is NULL when unused.
+ *   mask     the 1-bit ReLU mask: one byte per float4 of y, bit j = element j > 0, ld / 4 bytes per row.  The forward writes it,
+ *            the two backward passes read it INSTEAD of y (y is then ignored and may be NULL; without a mask y is required): the
+ *            same results bit for bit, a third less HBM traffic in the reduce.  Rows of 4-element groups only: with a mask, n and
+ *            ld must be multiples of 4 and every tensor pointer 16-byte aligned, else SAR_E_UNSUP.
+ *   amax_*   an operand-bound cell of the split arithmetic (cells: see sar_amax_f32), RAISED to the largest |value| the pass
+ *            wrote to that tensor -- what a separate sar_amax_f32 pass over it would give, without reading it again (28 such
+ *            passes cost 2.1 ms of a 39 ms f32_split step).  With or without a mask.
+ *
+ * Forward:  y = relu(u*scale[c]+shift[c] + res) ; mask (optional) ; amax_y (optional)
+ *   res_kind 0: none ; 1: identity (res = r) ; 2: conv residual (res = r*res_scale[c]+res_shift[c])
  * ------------------------------------------------------------------------------------------------ */
-int sar_bn_add_relu_fwd_f32(const float* u, const float* sc, const float* sh, int res_kind, const float* r,
-                            const float* rsc, const float* rsh, float* y, int C, int64_t n, int64_t ld, sar_stream_t s);
-/* backward pass 1: dz = (y>0)?dy:0 ; partials[C][nparts][4] = (sum dz, sum dz*(u-mu[c]), sum dz*(r-mr[c]), 0);
- * mu / mr (the batch means) may be NULL = 0 */
-int sar_bn_add_relu_bwd_reduce_f32(const float* dy, const float* y, const float* u, const float* r,
-                                   const float* mu, const float* mr, float* partials, int nparts, int C, int64_t n, int64_t ld, sar_stream_t s);
-/* The block tail with a 1-bit ReLU mask (fp32 rows of 4-element groups: n and ld multiples of 4, 16-byte aligned pointers, else
- * SAR_E_UNSUP): the forward also writes mask[c][i / 4] (one byte per float4 of y, bit j = element j > 0; ld / 4 bytes per row)
- * and the two backward passes read it instead of y: the same results bit for bit, a third less HBM traffic in the reduce. */
-int sar_bn_add_relu_fwd_mask_f32(const float* u, const float* scale, const float* shift, int res_kind, const float* r,
-                                 const float* res_scale, const float* res_shift, float* y, void* mask, int C, int64_t n, int64_t ld,
-                                 sar_stream_t s);
-int sar_bn_add_relu_bwd_reduce_mask_f32(const float* dy, const void* mask, const float* u, const float* r,
-                                        const float* mu, const float* mr, float* partials, int nparts, int C, int64_t n, int64_t ld,
-                                        sar_stream_t s);
-int sar_bn_add_relu_bwd_apply_mask_f32(const float* dy, const void* mask, const float* u, const float* r,
-                                       const float* k1, const float* k2, const float* k3,
-                                       const float* rk1, const float* rk2, const float* rk3,
-                                       float* du, float* dr, float* dz_out, int C, int64_t n, int64_t ld, sar_stream_t s);
-/* The same reduction (gradient of `relu(bn(u) + res)`, models/stgcn.py:37,56,62-63 and models/resnet18.py:46-63 under
- * main_gnn.py:233 / loss.backward()) with the BatchNorm-backward finalisation folded in ("tail"): the LAST workgroup of every channel to
- * finish (an integer ticket per channel, agent-scope release / acquire; no float atomics, every sum in a fixed order) adds the
- * channel's partials in fp64 and writes what sar_bn_bwd_finalize_f32(centered) would: dgamma, dbeta, k1, k2, k3 of the
- * block's BatchNorm and, when r != NULL, of the residual branch's -- one small dependent launch (or two) less on the critical
- * chain of every block.  ticket: C (f32) / ceil(C/8) (cn8) ints, zero before the first use; the kernel leaves them zero. */
+int sar_bn_add_relu_fwd_f32(const float* u, const float* scale, const float* shift, int res_kind, const float* r,
+                            const float* res_scale, const float* res_shift, float* y, void* mask, uint32_t* amax_y,
+                            int C, int64_t n, int64_t ld, sar_stream_t s);
+/* Backward pass 1: dz = (y>0)?dy:0 ; partials[C][nparts][4] = (sum dz, sum dz*(u-mu[c]), sum dz*(r-mr[c]), 0); mu / mr (the batch
+ * means) may be NULL = 0.
+ *   tail (optional): the BatchNorm-backward finalisation folded in.  The LAST workgroup of every channel to finish (an integer
+ *   ticket per channel, agent-scope release / acquire; no float atomics, every sum in a fixed order) adds the channel's partials
+ *   in fp64 and writes what sar_bn_bwd_finalize_f32(centered) would: dgamma, dbeta, k1, k2, k3 of the block's BatchNorm and, when
+ *   r != NULL, of the residual branch's -- one small dependent launch (or two) less on the critical chain of every block.
+ *   Required with a tail: ticket (C (f32) / ceil(C/8) (cn8) ints, zero before the first use; the kernel leaves them zero),
+ *   count > 0, rstd, k1..k3, the residual branch's rrstd and rk1..rk3 when r != NULL, and 16-byte aligned partials. */
 typedef struct sar_bn_tail {
   int32_t* ticket;
   double count;                                   /* elements per channel (N*T*V) */
@@ -355,30 +351,19 @@ typedef struct sar_bn_tail {
   const float* rgamma; const float* rrstd;        /* BatchNorm of the residual branch (r != NULL), mean = mr */
   float* rdgamma; float* rdbeta; float* rk1; float* rk2; float* rk3;
 } sar_bn_tail;
-int sar_bn_add_relu_bwd_reduce_tail_f32(const float* dy, const float* y, const float* u, const float* r,
-                                        const float* mu, const float* mr, float* partials, int nparts, int C, int64_t n, int64_t ld,
-                                        const sar_bn_tail* tail, sar_stream_t s);
-/* backward pass 2: du = k1*dz+k2*u+k3 ; dr = rk1*dz+rk2*r+rk3 (if dr != NULL) ; dz_out = dz (if != NULL) */
-int sar_bn_add_relu_bwd_apply_f32(const float* dy, const float* y, const float* u, const float* r,
+int sar_bn_add_relu_bwd_reduce_f32(const float* dy, const float* y, const void* mask, const float* u, const float* r,
+                                   const float* mu, const float* mr, float* partials, int nparts, int C, int64_t n, int64_t ld,
+                                   const sar_bn_tail* tail, sar_stream_t s);
+/* Backward pass 2: du = k1*dz+k2*u+k3 ; dr = rk1*dz+rk2*r+rk3 (if dr != NULL) ; dz_out = dz (if != NULL) ; amax_du, amax_dr
+ * (optional; amax_dr needs dr: it bounds the operand of the residual branch's dense 1x1 data gradient) */
+int sar_bn_add_relu_bwd_apply_f32(const float* dy, const float* y, const void* mask, const float* u, const float* r,
                                   const float* k1, const float* k2, const float* k3,
                                   const float* rk1, const float* rk2, const float* rk3,
-                                  float* du, float* dr, float* dz_out, int C, int64_t n, int64_t ld, sar_stream_t s);
-/* The same passes with an operand-bound by-product for the split arithmetic (cells: see sar_amax_f32): amax_y / amax_du /
- * amax_out is RAISED to the largest |value| the pass wrote to y / du / out -- what a separate sar_amax_f32 pass over that tensor
- * would give, without reading it again (28 such passes cost 2.1 ms of a 39 ms f32_split step). */
-int sar_bn_add_relu_fwd_mask_amax_f32(const float* u, const float* scale, const float* shift, int res_kind, const float* r,
-                                      const float* res_scale, const float* res_shift, float* y, void* mask, uint32_t* amax_y,
-                                      int C, int64_t n, int64_t ld, sar_stream_t s);
-int sar_bn_add_relu_bwd_apply_mask_amax_f32(const float* dy, const void* mask, const float* u, const float* r,
-                                            const float* k1, const float* k2, const float* k3,
-                                            const float* rk1, const float* rk2, const float* rk3,
-                                            float* du, float* dr, float* dz_out, uint32_t* amax_du, uint32_t* amax_dr, int C, int64_t n,
-                                            int64_t ld, sar_stream_t s);   /* amax_dr (may be NULL): the same for dr -- the operand of the residual branch's dense 1x1 data gradient (round 6) */
-int sar_affine2_amax_f32(const float* a, const float* b, const float* k1, const float* k2, const float* k3,
-                         float* out, uint32_t* amax_out, int C, int64_t n, int64_t ld, sar_stream_t s);
-/* generic row-affine: out = k1[c]*a + k2[c]*b + k3[c]  (BN backward apply: dg from dz1 and g) */
+                                  float* du, float* dr, float* dz_out, uint32_t* amax_du, uint32_t* amax_dr,
+                                  int C, int64_t n, int64_t ld, sar_stream_t s);
+/* generic row-affine: out = k1[c]*a + k2[c]*b + k3[c]  (BN backward apply: dg from dz1 and g) ; amax_out (optional) */
 int sar_affine2_f32(const float* a, const float* b, const float* k1, const float* k2, const float* k3,
-                    float* out, int C, int64_t n, int64_t ld, sar_stream_t s);
+                    float* out, uint32_t* amax_out, int C, int64_t n, int64_t ld, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
  * Head, models/stgcn.py:153-158: GlobalAveragePooling2D over (T,V), mean over the M persons,
@@ -877,30 +862,18 @@ int sar_conv_gemm_cn8(const sar_conv_desc* d, const void* packed_w, sar_stream_t
  * frames of one sequence; nsplit slabs as for sar_conv_wgrad_f32. */
 int sar_conv_wgrad_cn8_tile_frames(int mode);
 int sar_conv_wgrad_cn8(const sar_wgrad_desc* d, int slice0_identity, sar_stream_t s);
-/* Block tail and BatchNorm-backward passes on CN8 tensors: semantics and partial layouts of the *_f32 functions of the
- * same name (C = channels, n = columns, ld = units per plane). */
+/* Block tail and BatchNorm-backward passes on CN8 tensors: semantics, optional pointers and partial layouts of the *_f32
+ * functions of the same name (C = channels, n = columns, ld = units per plane), without the amax cells.  Every CN8 tensor must be
+ * 16-byte aligned (SAR_E_ARG otherwise).  mask: one byte per unit, mask[g][col] bit j = stored channel 8 g + j is > 0, ld bytes
+ * per plane; read by the two backward passes instead of the 16-byte unit of y -- the same results bit for bit, 115 MB less HBM
+ * traffic per pass at the NTU shapes. */
 int sar_bn_add_relu_fwd_cn8(const void* u, const float* scale, const float* shift, int res_kind, const void* r,
-                            const float* res_scale, const float* res_shift, void* y, int C, int64_t n, int64_t ld,
+                            const float* res_scale, const float* res_shift, void* y, void* mask, int C, int64_t n, int64_t ld,
                             sar_stream_t s);
-int sar_bn_add_relu_bwd_reduce_cn8(const void* dy, const void* y, const void* u, const void* r, const float* mean_u,
-                                   const float* mean_r, float* partials, int nparts, int C, int64_t n, int64_t ld,
-                                   sar_stream_t s);
-/* The block tail with a 1-bit ReLU mask: the forward also writes mask[g][col] (one byte per unit, bit j = stored channel 8 g + j
- * is > 0; ld bytes per plane), and the two backward passes read that byte instead of the 16-byte unit of y -- the same
- * results bit for bit, 115 MB less HBM traffic per pass at the NTU shapes (models/stgcn.py:37,62-63 and their gradients). */
-int sar_bn_add_relu_fwd_mask_cn8(const void* u, const float* scale, const float* shift, int res_kind, const void* r,
-                                 const float* res_scale, const float* res_shift, void* y, void* mask, int C, int64_t n, int64_t ld,
-                                 sar_stream_t s);
-int sar_bn_add_relu_bwd_reduce_mask_cn8(const void* dy, const void* mask, const void* u, const void* r, const float* mean_u,
-                                        const float* mean_r, float* partials, int nparts, int C, int64_t n, int64_t ld,
-                                        sar_stream_t s);
-int sar_bn_add_relu_bwd_apply_mask_cn8(const void* dy, const void* mask, const void* u, const void* r, const float* k1,
-                                       const float* k2, const float* k3, const float* rk1, const float* rk2, const float* rk3,
-                                       void* du, void* dr, void* dz_out, int C, int64_t n, int64_t ld, sar_stream_t s);
-int sar_bn_add_relu_bwd_reduce_tail_cn8(const void* dy, const void* y, const void* u, const void* r, const float* mean_u,
-                                        const float* mean_r, float* partials, int nparts, int C, int64_t n, int64_t ld,
-                                        const sar_bn_tail* tail, sar_stream_t s);
-int sar_bn_add_relu_bwd_apply_cn8(const void* dy, const void* y, const void* u, const void* r, const float* k1,
+int sar_bn_add_relu_bwd_reduce_cn8(const void* dy, const void* y, const void* mask, const void* u, const void* r,
+                                   const float* mean_u, const float* mean_r, float* partials, int nparts, int C, int64_t n,
+                                   int64_t ld, const sar_bn_tail* tail, sar_stream_t s);
+int sar_bn_add_relu_bwd_apply_cn8(const void* dy, const void* y, const void* mask, const void* u, const void* r, const float* k1,
                                   const float* k2, const float* k3, const float* rk1, const float* rk2, const float* rk3,
                                   void* du, void* dr, void* dz_out, int C, int64_t n, int64_t ld, sar_stream_t s);
 int sar_affine2_cn8(const void* a, const void* b, const float* k1, const float* k2, const float* k3, void* out, int C,

@@ -18,7 +18,7 @@ void sar_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* sar_last_error_string(void) { return g_err; }
-extern "C" int sar_version(void) { return 100; }
+extern "C" int sar_version(void) { return 101; }
 extern "C" int sar_context_create(sar_context** out) {
   SAR_REQUIRE(out != nullptr, "sar_context_create: null output pointer");
   *out = nullptr;
@@ -382,7 +382,7 @@ __device__ __forceinline__ void block_amax(unsigned m, unsigned* __restrict__ ce
 }
 
 // mask (VEC == 4 only): one byte per float4 of y, bit j = element j > 0, row stride ldm / 4 bytes -- read by the two backward
-// passes instead of y (sar_bn_add_relu_*_mask_f32)
+// passes instead of y (the `mask` argument of sar_bn_add_relu_*_f32)
 template <int VEC>
 __global__ __launch_bounds__(TPB) void bn_add_relu_fwd_kernel(const float* __restrict__ u, const float* __restrict__ sc,
                                                               const float* __restrict__ sh, int res_kind,
@@ -825,169 +825,96 @@ extern "C" int sar_data_bn_bwd_reduce_cn8(const float* x, int N, int C, int T, i
   return 0;
 }
 
+// Block tail (include/sar_hip.h): one entry point per pass; mask, the amax cells and tail are optional (NULL = unused).
+// Every instantiation of its kernels, listed once: the compiler emits them in the order of their first use, so this list (not the
+// layout of the entry points below) fixes their order in the code object, and a diff of the device assembly between two builds
+// shows kernels that changed and nothing else.
+[[maybe_unused]] static const void* const block_tail_kernels[] = {
+    (const void*)bn_add_relu_fwd_kernel<4>,              (const void*)bn_add_relu_fwd_kernel<1>,
+    (const void*)bn_add_relu_bwd_reduce_kernel<4, false>, (const void*)bn_add_relu_bwd_apply_kernel<4>,
+    (const void*)bn_add_relu_bwd_reduce_kernel<1, false>, (const void*)bn_add_relu_bwd_reduce_kernel<4, true>,
+    (const void*)bn_add_relu_bwd_reduce_kernel<1, true>,  (const void*)bn_add_relu_bwd_apply_kernel<1>,
+    (const void*)affine2_kernel<4>,                      (const void*)affine2_kernel<1>};
+
+static int mask_rows_unsup(const char* fn, int64_t n, int64_t ldm) {
+  sar_set_error("%s: with a mask, rows must be 16-byte aligned multiples of 4 elements (n=%lld, ld=%lld)", fn, (long long)n, (long long)ldm);
+  return SAR_E_UNSUP;
+}
+
 extern "C" int sar_bn_add_relu_fwd_f32(const float* u, const float* sc, const float* sh, int res_kind, const float* r,
-                                       const float* rsc, const float* rsh, float* y, int C, int64_t n, int64_t ldm,
-                                       sar_stream_t s) {
-  SAR_REQUIRE(u && sc && sh && y && C > 0 && n > 0 && ldm >= n, "sar_bn_add_relu_fwd: bad arguments");
+                                       const float* rsc, const float* rsh, float* y, void* mask, uint32_t* amax_y, int C, int64_t n,
+                                       int64_t ldm, sar_stream_t s) {
+  SAR_REQUIRE(u && sc && sh && y && C > 0 && n > 0 && ldm >= n, "sar_bn_add_relu_fwd_f32: bad arguments");
   SAR_REQUIRE(res_kind >= 0 && res_kind <= 2 && (res_kind == 0 || r) && (res_kind != 2 || (rsc && rsh)),
-              "sar_bn_add_relu_fwd: residual arguments");
+              "sar_bn_add_relu_fwd_f32: residual arguments");
   if (vec4_ok(n, ldm, {u, r, y})) {
     hipLaunchKernelGGL(bn_add_relu_fwd_kernel<4>, dim3(row_blocks(n, 4), C), dim3(TPB), 0, as_stream(s), u, sc, sh,
-                       res_kind, r, rsc, rsh, y, n, ldm);
+                       res_kind, r, rsc, rsh, y, n, ldm, (unsigned char*)mask, amax_y);
   } else {
+    if (mask) return mask_rows_unsup("sar_bn_add_relu_fwd_f32", n, ldm);
     hipLaunchKernelGGL(bn_add_relu_fwd_kernel<1>, dim3(row_blocks(n, 1), C), dim3(TPB), 0, as_stream(s), u, sc, sh,
-                       res_kind, r, rsc, rsh, y, n, ldm);
+                       res_kind, r, rsc, rsh, y, n, ldm, (unsigned char*)nullptr, amax_y);
   }
   SAR_LAUNCH_CHECK("sar_bn_add_relu_fwd_f32");
   return 0;
 }
 
-// the block tail with a 1-bit ReLU mask (include/sar_hip.h): rows of 4-element groups only (n, ld multiples of 4, 16-byte aligned)
-static int bn_add_relu_fwd_mask_impl(const float* u, const float* sc, const float* sh, int res_kind, const float* r,
-                                     const float* rsc, const float* rsh, float* y, void* mask, uint32_t* amax, int C, int64_t n, int64_t ldm,
-                                     sar_stream_t s) {
-  SAR_REQUIRE(u && sc && sh && y && mask && C > 0 && n > 0 && ldm >= n, "sar_bn_add_relu_fwd_mask: bad arguments");
-  SAR_REQUIRE(res_kind >= 0 && res_kind <= 2 && (res_kind == 0 || r) && (res_kind != 2 || (rsc && rsh)),
-              "sar_bn_add_relu_fwd_mask: residual arguments");
-  if (!vec4_ok(n, ldm, {u, r, y})) {
-    sar_set_error("sar_bn_add_relu_fwd_mask: rows must be 16-byte aligned multiples of 4 elements (n=%lld, ld=%lld)", (long long)n, (long long)ldm);
-    return SAR_E_UNSUP;
+extern "C" int sar_bn_add_relu_bwd_reduce_f32(const float* dy, const float* y, const void* mask, const float* u, const float* r,
+                                              const float* mu, const float* mr, float* partials, int nparts, int C, int64_t n,
+                                              int64_t ldm, const sar_bn_tail* tail, sar_stream_t s) {
+  SAR_REQUIRE(dy && (y || mask) && u && partials && nparts > 0 && nparts <= 65535 && C > 0 && n > 0 && ldm >= n,
+              "sar_bn_add_relu_bwd_reduce_f32: bad arguments");
+  if (tail) {
+    SAR_REQUIRE(tail->ticket && tail->count > 0 && tail->rstd && tail->k1 && tail->k2 && tail->k3,
+                "sar_bn_add_relu_bwd_reduce_f32: tail: ticket, count, rstd and k1..k3 are required");
+    SAR_REQUIRE(!r || (tail->rrstd && tail->rk1 && tail->rk2 && tail->rk3), "sar_bn_add_relu_bwd_reduce_f32: tail: residual-branch outputs");
+    SAR_REQUIRE(((uintptr_t)partials & 15) == 0, "sar_bn_add_relu_bwd_reduce_f32: tail: partials must be 16-byte aligned");
   }
-  hipLaunchKernelGGL(bn_add_relu_fwd_kernel<4>, dim3(row_blocks(n, 4), C), dim3(TPB), 0, as_stream(s), u, sc, sh, res_kind, r, rsc,
-                     rsh, y, n, ldm, (unsigned char*)mask, amax);
-  SAR_LAUNCH_CHECK("sar_bn_add_relu_fwd_mask_f32");
-  return 0;
-}
-extern "C" int sar_bn_add_relu_fwd_mask_f32(const float* u, const float* sc, const float* sh, int res_kind, const float* r,
-                                            const float* rsc, const float* rsh, float* y, void* mask, int C, int64_t n, int64_t ldm,
-                                            sar_stream_t s) {
-  return bn_add_relu_fwd_mask_impl(u, sc, sh, res_kind, r, rsc, rsh, y, mask, nullptr, C, n, ldm, s);
-}
-extern "C" int sar_bn_add_relu_fwd_mask_amax_f32(const float* u, const float* sc, const float* sh, int res_kind, const float* r,
-                                                 const float* rsc, const float* rsh, float* y, void* mask, uint32_t* amax_y, int C,
-                                                 int64_t n, int64_t ldm, sar_stream_t s) {
-  SAR_REQUIRE(amax_y != nullptr, "sar_bn_add_relu_fwd_mask_amax: null cell");
-  return bn_add_relu_fwd_mask_impl(u, sc, sh, res_kind, r, rsc, rsh, y, mask, amax_y, C, n, ldm, s);
-}
-
-extern "C" int sar_bn_add_relu_bwd_reduce_mask_f32(const float* dy, const void* mask, const float* u, const float* r,
-                                                   const float* mu, const float* mr, float* partials, int nparts, int C, int64_t n,
-                                                   int64_t ldm, sar_stream_t s) {
-  SAR_REQUIRE(dy && mask && u && partials && nparts > 0 && nparts <= 65535 && C > 0 && n > 0 && ldm >= n,
-              "sar_bn_add_relu_bwd_reduce_mask: bad arguments");
-  if (!vec4_ok(n, ldm, {dy, u, r})) {
-    sar_set_error("sar_bn_add_relu_bwd_reduce_mask: rows must be 16-byte aligned multiples of 4 elements");
-    return SAR_E_UNSUP;
-  }
-  hipLaunchKernelGGL((bn_add_relu_bwd_reduce_kernel<4, false>), dim3(nparts, C), dim3(TPB), 0, as_stream(s), dy, (const float*)nullptr,
-                     u, r, mu, mr, partials, n, ldm, sar_bn_tail(), (const unsigned char*)mask);
-  SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_reduce_mask_f32");
-  return 0;
-}
-
-static int bn_add_relu_bwd_apply_mask_impl(const float* dy, const void* mask, const float* u, const float* r,
-                                           const float* k1, const float* k2, const float* k3, const float* rk1,
-                                           const float* rk2, const float* rk3, float* du, float* dr, float* dz_out, uint32_t* amax,
-                                           int C, int64_t n, int64_t ldm, sar_stream_t s, uint32_t* amax_r = nullptr) {
-  SAR_REQUIRE(dy && mask && u && k1 && k2 && k3 && du && C > 0 && n > 0 && ldm >= n, "sar_bn_add_relu_bwd_apply_mask: bad arguments");
-  SAR_REQUIRE(!dr || (r && rk1 && rk2 && rk3), "sar_bn_add_relu_bwd_apply_mask: residual arguments");
-  if (!vec4_ok(n, ldm, {dy, u, r, du, dr, dz_out})) {
-    sar_set_error("sar_bn_add_relu_bwd_apply_mask: rows must be 16-byte aligned multiples of 4 elements");
-    return SAR_E_UNSUP;
-  }
-  hipLaunchKernelGGL(bn_add_relu_bwd_apply_kernel<4>, dim3(row_blocks(n, 4), C), dim3(TPB), 0, as_stream(s), dy, (const float*)nullptr,
-                     u, r, k1, k2, k3, rk1, rk2, rk3, du, dr, dz_out, n, ldm, (const unsigned char*)mask, amax, amax_r);
-  SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_apply_mask_f32");
-  return 0;
-}
-extern "C" int sar_bn_add_relu_bwd_apply_mask_f32(const float* dy, const void* mask, const float* u, const float* r,
-                                                  const float* k1, const float* k2, const float* k3, const float* rk1,
-                                                  const float* rk2, const float* rk3, float* du, float* dr, float* dz_out,
-                                                  int C, int64_t n, int64_t ldm, sar_stream_t s) {
-  return bn_add_relu_bwd_apply_mask_impl(dy, mask, u, r, k1, k2, k3, rk1, rk2, rk3, du, dr, dz_out, nullptr, C, n, ldm, s);
-}
-extern "C" int sar_bn_add_relu_bwd_apply_mask_amax_f32(const float* dy, const void* mask, const float* u, const float* r,
-                                                       const float* k1, const float* k2, const float* k3, const float* rk1,
-                                                       const float* rk2, const float* rk3, float* du, float* dr, float* dz_out,
-                                                       uint32_t* amax_du, uint32_t* amax_dr, int C, int64_t n, int64_t ldm, sar_stream_t s) {
-  SAR_REQUIRE(amax_du != nullptr, "sar_bn_add_relu_bwd_apply_mask_amax: null cell");
-  SAR_REQUIRE(!amax_dr || dr, "sar_bn_add_relu_bwd_apply_mask_amax: amax_dr without dr");
-  return bn_add_relu_bwd_apply_mask_impl(dy, mask, u, r, k1, k2, k3, rk1, rk2, rk3, du, dr, dz_out, amax_du, C, n, ldm, s, amax_dr);
-}
-
-extern "C" int sar_bn_add_relu_bwd_reduce_f32(const float* dy, const float* y, const float* u, const float* r,
-                                              const float* mu, const float* mr, float* partials, int nparts, int C, int64_t n, int64_t ldm, sar_stream_t s) {
-  SAR_REQUIRE(dy && y && u && partials && nparts > 0 && nparts <= 65535 && C > 0 && n > 0 && ldm >= n,
-              "sar_bn_add_relu_bwd_reduce: bad arguments");
-  if (vec4_ok(n, ldm, {dy, y, u, r})) {
-    hipLaunchKernelGGL(bn_add_relu_bwd_reduce_kernel<4>, dim3(nparts, C), dim3(TPB), 0, as_stream(s), dy, y, u, r,
-                       mu, mr, partials, n, ldm);
-  } else {
-    hipLaunchKernelGGL(bn_add_relu_bwd_reduce_kernel<1>, dim3(nparts, C), dim3(TPB), 0, as_stream(s), dy, y, u, r,
-                       mu, mr, partials, n, ldm);
-  }
+  const unsigned char* m = (const unsigned char*)mask;
+  if (m) y = nullptr;   // the ReLU comes from the mask
+  const bool vec4 = vec4_ok(n, ldm, {dy, y, u, r});
+  if (m && !vec4) return mask_rows_unsup("sar_bn_add_relu_bwd_reduce_f32", n, ldm);
+  const auto kernel = vec4 ? (tail ? bn_add_relu_bwd_reduce_kernel<4, true> : bn_add_relu_bwd_reduce_kernel<4, false>)
+                           : (tail ? bn_add_relu_bwd_reduce_kernel<1, true> : bn_add_relu_bwd_reduce_kernel<1, false>);
+  hipLaunchKernelGGL(kernel, dim3(nparts, C), dim3(TPB), 0, as_stream(s), dy, y, u, r, mu, mr, partials, n, ldm,
+                     tail ? *tail : sar_bn_tail(), m);
   SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_reduce_f32");
   return 0;
 }
 
-extern "C" int sar_bn_add_relu_bwd_reduce_tail_f32(const float* dy, const float* y, const float* u, const float* r,
-                                                   const float* mu, const float* mr, float* partials, int nparts, int C, int64_t n,
-                                                   int64_t ldm, const sar_bn_tail* tail, sar_stream_t s) {
-  SAR_REQUIRE(dy && y && u && partials && nparts > 0 && nparts <= 65535 && C > 0 && n > 0 && ldm >= n,
-              "sar_bn_add_relu_bwd_reduce_tail: bad arguments");
-  SAR_REQUIRE(tail && tail->ticket && tail->count > 0 && tail->rstd && tail->k1 && tail->k2 && tail->k3,
-              "sar_bn_add_relu_bwd_reduce_tail: ticket, count, rstd and k1..k3 are required");
-  SAR_REQUIRE(!r || (tail->rrstd && tail->rk1 && tail->rk2 && tail->rk3), "sar_bn_add_relu_bwd_reduce_tail: residual-branch outputs");
-  SAR_REQUIRE(((uintptr_t)partials & 15) == 0, "sar_bn_add_relu_bwd_reduce_tail: partials must be 16-byte aligned");
-  if (vec4_ok(n, ldm, {dy, y, u, r})) {
-    hipLaunchKernelGGL((bn_add_relu_bwd_reduce_kernel<4, true>), dim3(nparts, C), dim3(TPB), 0, as_stream(s), dy, y, u, r, mu, mr,
-                       partials, n, ldm, *tail);
-  } else {
-    hipLaunchKernelGGL((bn_add_relu_bwd_reduce_kernel<1, true>), dim3(nparts, C), dim3(TPB), 0, as_stream(s), dy, y, u, r, mu, mr,
-                       partials, n, ldm, *tail);
-  }
-  SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_reduce_tail_f32");
-  return 0;
-}
-
-extern "C" int sar_bn_add_relu_bwd_apply_f32(const float* dy, const float* y, const float* u, const float* r,
+extern "C" int sar_bn_add_relu_bwd_apply_f32(const float* dy, const float* y, const void* mask, const float* u, const float* r,
                                              const float* k1, const float* k2, const float* k3, const float* rk1,
                                              const float* rk2, const float* rk3, float* du, float* dr, float* dz_out,
-                                             int C, int64_t n, int64_t ldm, sar_stream_t s) {
-  SAR_REQUIRE(dy && y && u && k1 && k2 && k3 && du && C > 0 && n > 0 && ldm >= n, "sar_bn_add_relu_bwd_apply: bad arguments");
-  SAR_REQUIRE(!dr || (r && rk1 && rk2 && rk3), "sar_bn_add_relu_bwd_apply: residual arguments");
+                                             uint32_t* amax_du, uint32_t* amax_dr, int C, int64_t n, int64_t ldm, sar_stream_t s) {
+  SAR_REQUIRE(dy && (y || mask) && u && k1 && k2 && k3 && du && C > 0 && n > 0 && ldm >= n, "sar_bn_add_relu_bwd_apply_f32: bad arguments");
+  SAR_REQUIRE(!dr || (r && rk1 && rk2 && rk3), "sar_bn_add_relu_bwd_apply_f32: residual arguments");
+  SAR_REQUIRE(!amax_dr || dr, "sar_bn_add_relu_bwd_apply_f32: amax_dr without dr");
+  const unsigned char* m = (const unsigned char*)mask;
+  if (m) y = nullptr;   // the ReLU comes from the mask
   if (vec4_ok(n, ldm, {dy, y, u, r, du, dr, dz_out})) {
     hipLaunchKernelGGL(bn_add_relu_bwd_apply_kernel<4>, dim3(row_blocks(n, 4), C), dim3(TPB), 0, as_stream(s), dy, y, u,
-                       r, k1, k2, k3, rk1, rk2, rk3, du, dr, dz_out, n, ldm);
+                       r, k1, k2, k3, rk1, rk2, rk3, du, dr, dz_out, n, ldm, m, amax_du, amax_dr);
   } else {
+    if (m) return mask_rows_unsup("sar_bn_add_relu_bwd_apply_f32", n, ldm);
     hipLaunchKernelGGL(bn_add_relu_bwd_apply_kernel<1>, dim3(row_blocks(n, 1), C), dim3(TPB), 0, as_stream(s), dy, y, u,
-                       r, k1, k2, k3, rk1, rk2, rk3, du, dr, dz_out, n, ldm);
+                       r, k1, k2, k3, rk1, rk2, rk3, du, dr, dz_out, n, ldm, m, amax_du, amax_dr);
   }
   SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_apply_f32");
   return 0;
 }
 
-static int affine2_impl(const float* a, const float* b, const float* k1, const float* k2, const float* k3,
-                        float* out, uint32_t* amax, int C, int64_t n, int64_t ldm, sar_stream_t s) {
-  SAR_REQUIRE(a && b && k1 && k2 && k3 && out && C > 0 && n > 0 && ldm >= n, "sar_affine2: bad arguments");
+extern "C" int sar_affine2_f32(const float* a, const float* b, const float* k1, const float* k2, const float* k3,
+                               float* out, uint32_t* amax_out, int C, int64_t n, int64_t ldm, sar_stream_t s) {
+  SAR_REQUIRE(a && b && k1 && k2 && k3 && out && C > 0 && n > 0 && ldm >= n, "sar_affine2_f32: bad arguments");
   if (vec4_ok(n, ldm, {a, b, out})) {
     hipLaunchKernelGGL(affine2_kernel<4>, dim3(row_blocks(n, 4), C), dim3(TPB), 0, as_stream(s), a, b, k1, k2, k3, out, n,
-                       ldm, amax);
+                       ldm, amax_out);
   } else {
     hipLaunchKernelGGL(affine2_kernel<1>, dim3(row_blocks(n, 1), C), dim3(TPB), 0, as_stream(s), a, b, k1, k2, k3, out, n,
-                       ldm, amax);
+                       ldm, amax_out);
   }
   SAR_LAUNCH_CHECK("sar_affine2_f32");
   return 0;
-}
-extern "C" int sar_affine2_f32(const float* a, const float* b, const float* k1, const float* k2, const float* k3,
-                               float* out, int C, int64_t n, int64_t ldm, sar_stream_t s) {
-  return affine2_impl(a, b, k1, k2, k3, out, nullptr, C, n, ldm, s);
-}
-extern "C" int sar_affine2_amax_f32(const float* a, const float* b, const float* k1, const float* k2, const float* k3,
-                                    float* out, uint32_t* amax_out, int C, int64_t n, int64_t ldm, sar_stream_t s) {
-  SAR_REQUIRE(amax_out != nullptr, "sar_affine2_amax: null cell");
-  return affine2_impl(a, b, k1, k2, k3, out, amax_out, C, n, ldm, s);
 }
 
 extern "C" int sar_pool_fwd_f32(const float* y, int64_t ldm, int C, int B, int TV, int Mp, float* feat, sar_stream_t s) {

@@ -319,97 +319,55 @@ inline bool al16(std::initializer_list<const void*> ptrs) {
 
 #define CN8_G(C) (((C) + 7) / 8)
 
+// Block tail on CN8 tensors (include/sar_hip.h): one entry point per pass; mask and tail are optional (NULL = unused)
 extern "C" int sar_bn_add_relu_fwd_cn8(const void* u, const float* sc, const float* sh, int res_kind, const void* r,
-                                       const float* rsc, const float* rsh, void* y, int C, int64_t n, int64_t ld,
+                                       const float* rsc, const float* rsh, void* y, void* mask, int C, int64_t n, int64_t ld,
                                        sar_stream_t s) {
   SAR_REQUIRE(u && sc && sh && y && C > 0 && n > 0 && ld >= n, "sar_bn_add_relu_fwd_cn8: bad arguments");
   SAR_REQUIRE(res_kind >= 0 && res_kind <= 2 && (res_kind == 0 || r) && (res_kind != 2 || (rsc && rsh)),
               "sar_bn_add_relu_fwd_cn8: residual arguments");
   SAR_REQUIRE(al16({u, r, y}), "sar_bn_add_relu_fwd_cn8: CN8 tensors must be 16-byte aligned");
   hipLaunchKernelGGL(bn_add_relu_fwd_cn8_kernel, dim3(unit_blocks(n, EW_U), CN8_G(C)), dim3(TPB), 0, as_stream(s), (const uint4*)u, sc,
-                     sh, res_kind, (const uint4*)r, rsc, rsh, (uint4*)y, C, n, ld);
+                     sh, res_kind, (const uint4*)r, rsc, rsh, (uint4*)y, C, n, ld, (unsigned char*)mask);
   SAR_LAUNCH_CHECK("sar_bn_add_relu_fwd_cn8");
   return 0;
 }
 
-extern "C" int sar_bn_add_relu_fwd_mask_cn8(const void* u, const float* sc, const float* sh, int res_kind, const void* r,
-                                            const float* rsc, const float* rsh, void* y, void* mask, int C, int64_t n, int64_t ld,
-                                            sar_stream_t s) {
-  SAR_REQUIRE(u && sc && sh && y && mask && C > 0 && n > 0 && ld >= n, "sar_bn_add_relu_fwd_mask_cn8: bad arguments");
-  SAR_REQUIRE(res_kind >= 0 && res_kind <= 2 && (res_kind == 0 || r) && (res_kind != 2 || (rsc && rsh)),
-              "sar_bn_add_relu_fwd_mask_cn8: residual arguments");
-  SAR_REQUIRE(al16({u, r, y}), "sar_bn_add_relu_fwd_mask_cn8: CN8 tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(bn_add_relu_fwd_cn8_kernel, dim3(unit_blocks(n, EW_U), CN8_G(C)), dim3(TPB), 0, as_stream(s), (const uint4*)u, sc,
-                     sh, res_kind, (const uint4*)r, rsc, rsh, (uint4*)y, C, n, ld, (unsigned char*)mask);
-  SAR_LAUNCH_CHECK("sar_bn_add_relu_fwd_mask_cn8");
-  return 0;
-}
-
-extern "C" int sar_bn_add_relu_bwd_reduce_cn8(const void* dy, const void* y, const void* u, const void* r, const float* mean_u,
-                                              const float* mean_r, float* partials, int nparts, int C, int64_t n, int64_t ld,
-                                              sar_stream_t s) {
-  SAR_REQUIRE(dy && y && u && partials && nparts > 0 && nparts <= 65535 && C > 0 && n > 0 && ld >= n,
+extern "C" int sar_bn_add_relu_bwd_reduce_cn8(const void* dy, const void* y, const void* mask, const void* u, const void* r,
+                                              const float* mean_u, const float* mean_r, float* partials, int nparts, int C, int64_t n,
+                                              int64_t ld, const sar_bn_tail* tail, sar_stream_t s) {
+  SAR_REQUIRE(dy && (y || mask) && u && partials && nparts > 0 && nparts <= 65535 && C > 0 && n > 0 && ld >= n,
               "sar_bn_add_relu_bwd_reduce_cn8: bad arguments");
+  if (mask) y = nullptr;   // the ReLU comes from the mask
   SAR_REQUIRE(al16({dy, y, u, r}), "sar_bn_add_relu_bwd_reduce_cn8: CN8 tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(bn_add_relu_bwd_reduce_cn8_kernel<false>, dim3(nparts, CN8_G(C)), dim3(TPB), 0, as_stream(s), (const uint4*)dy,
-                     (const uint4*)y, (const uint4*)u, (const uint4*)r, mean_u, mean_r, partials, C, n, ld, sar_bn_tail());
+  const dim3 grid(nparts, CN8_G(C));
+  if (!tail) {
+    hipLaunchKernelGGL(bn_add_relu_bwd_reduce_cn8_kernel<false>, grid, dim3(TPB), 0, as_stream(s), (const uint4*)dy, (const uint4*)y,
+                       (const uint4*)u, (const uint4*)r, mean_u, mean_r, partials, C, n, ld, sar_bn_tail(), (const unsigned char*)mask);
+  } else {
+    SAR_REQUIRE(tail->ticket && tail->count > 0 && tail->rstd && tail->k1 && tail->k2 && tail->k3,
+                "sar_bn_add_relu_bwd_reduce_cn8: tail: ticket, count, rstd and k1..k3 are required");
+    SAR_REQUIRE(!r || (tail->rrstd && tail->rk1 && tail->rk2 && tail->rk3), "sar_bn_add_relu_bwd_reduce_cn8: tail: residual-branch outputs");
+    SAR_REQUIRE(al16({partials}), "sar_bn_add_relu_bwd_reduce_cn8: tail: partials must be 16-byte aligned");
+    hipLaunchKernelGGL(bn_add_relu_bwd_reduce_cn8_kernel<true>, grid, dim3(TPB), 0, as_stream(s), (const uint4*)dy, (const uint4*)y,
+                       (const uint4*)u, (const uint4*)r, mean_u, mean_r, partials, C, n, ld, *tail, (const unsigned char*)mask);
+  }
   SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_reduce_cn8");
   return 0;
 }
 
-extern "C" int sar_bn_add_relu_bwd_reduce_mask_cn8(const void* dy, const void* mask, const void* u, const void* r,
-                                                   const float* mean_u, const float* mean_r, float* partials, int nparts, int C,
-                                                   int64_t n, int64_t ld, sar_stream_t s) {
-  SAR_REQUIRE(dy && mask && u && partials && nparts > 0 && nparts <= 65535 && C > 0 && n > 0 && ld >= n,
-              "sar_bn_add_relu_bwd_reduce_mask_cn8: bad arguments");
-  SAR_REQUIRE(al16({dy, u, r}), "sar_bn_add_relu_bwd_reduce_mask_cn8: CN8 tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(bn_add_relu_bwd_reduce_cn8_kernel<false>, dim3(nparts, CN8_G(C)), dim3(TPB), 0, as_stream(s), (const uint4*)dy,
-                     (const uint4*)nullptr, (const uint4*)u, (const uint4*)r, mean_u, mean_r, partials, C, n, ld, sar_bn_tail(),
-                     (const unsigned char*)mask);
-  SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_reduce_mask_cn8");
-  return 0;
-}
-
-extern "C" int sar_bn_add_relu_bwd_reduce_tail_cn8(const void* dy, const void* y, const void* u, const void* r, const float* mean_u,
-                                                   const float* mean_r, float* partials, int nparts, int C, int64_t n, int64_t ld,
-                                                   const sar_bn_tail* tail, sar_stream_t s) {
-  SAR_REQUIRE(dy && y && u && partials && nparts > 0 && nparts <= 65535 && C > 0 && n > 0 && ld >= n,
-              "sar_bn_add_relu_bwd_reduce_tail_cn8: bad arguments");
-  SAR_REQUIRE(al16({dy, y, u, r, partials}), "sar_bn_add_relu_bwd_reduce_tail_cn8: CN8 tensors and partials must be 16-byte aligned");
-  SAR_REQUIRE(tail && tail->ticket && tail->count > 0 && tail->rstd && tail->k1 && tail->k2 && tail->k3,
-              "sar_bn_add_relu_bwd_reduce_tail_cn8: ticket, count, rstd and k1..k3 are required");
-  SAR_REQUIRE(!r || (tail->rrstd && tail->rk1 && tail->rk2 && tail->rk3), "sar_bn_add_relu_bwd_reduce_tail_cn8: residual-branch outputs");
-  hipLaunchKernelGGL(bn_add_relu_bwd_reduce_cn8_kernel<true>, dim3(nparts, CN8_G(C)), dim3(TPB), 0, as_stream(s), (const uint4*)dy,
-                     (const uint4*)y, (const uint4*)u, (const uint4*)r, mean_u, mean_r, partials, C, n, ld, *tail);
-  SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_reduce_tail_cn8");
-  return 0;
-}
-
-extern "C" int sar_bn_add_relu_bwd_apply_cn8(const void* dy, const void* y, const void* u, const void* r, const float* k1,
-                                             const float* k2, const float* k3, const float* rk1, const float* rk2,
+extern "C" int sar_bn_add_relu_bwd_apply_cn8(const void* dy, const void* y, const void* mask, const void* u, const void* r,
+                                             const float* k1, const float* k2, const float* k3, const float* rk1, const float* rk2,
                                              const float* rk3, void* du, void* dr, void* dz_out, int C, int64_t n, int64_t ld,
                                              sar_stream_t s) {
-  SAR_REQUIRE(dy && y && u && k1 && k2 && k3 && du && C > 0 && n > 0 && ld >= n, "sar_bn_add_relu_bwd_apply_cn8: bad arguments");
+  SAR_REQUIRE(dy && (y || mask) && u && k1 && k2 && k3 && du && C > 0 && n > 0 && ld >= n, "sar_bn_add_relu_bwd_apply_cn8: bad arguments");
   SAR_REQUIRE(!dr || (r && rk1 && rk2 && rk3), "sar_bn_add_relu_bwd_apply_cn8: residual-branch arguments");
+  if (mask) y = nullptr;   // the ReLU comes from the mask
   SAR_REQUIRE(al16({dy, y, u, r, du, dr, dz_out}), "sar_bn_add_relu_bwd_apply_cn8: CN8 tensors must be 16-byte aligned");
   hipLaunchKernelGGL(bn_add_relu_bwd_apply_cn8_kernel, dim3(unit_blocks(n, EW_U), CN8_G(C)), dim3(TPB), 0, as_stream(s),
                      (const uint4*)dy, (const uint4*)y, (const uint4*)u, (const uint4*)r, k1, k2, k3, rk1, rk2, rk3, (uint4*)du,
-                     (uint4*)dr, (uint4*)dz_out, C, n, ld);
-  SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_apply_cn8");
-  return 0;
-}
-
-extern "C" int sar_bn_add_relu_bwd_apply_mask_cn8(const void* dy, const void* mask, const void* u, const void* r, const float* k1,
-                                                  const float* k2, const float* k3, const float* rk1, const float* rk2,
-                                                  const float* rk3, void* du, void* dr, void* dz_out, int C, int64_t n, int64_t ld,
-                                                  sar_stream_t s) {
-  SAR_REQUIRE(dy && mask && u && k1 && k2 && k3 && du && C > 0 && n > 0 && ld >= n, "sar_bn_add_relu_bwd_apply_mask_cn8: bad arguments");
-  SAR_REQUIRE(!dr || (r && rk1 && rk2 && rk3), "sar_bn_add_relu_bwd_apply_mask_cn8: residual-branch arguments");
-  SAR_REQUIRE(al16({dy, u, r, du, dr, dz_out}), "sar_bn_add_relu_bwd_apply_mask_cn8: CN8 tensors must be 16-byte aligned");
-  hipLaunchKernelGGL(bn_add_relu_bwd_apply_cn8_kernel, dim3(unit_blocks(n, EW_U), CN8_G(C)), dim3(TPB), 0, as_stream(s),
-                     (const uint4*)dy, (const uint4*)nullptr, (const uint4*)u, (const uint4*)r, k1, k2, k3, rk1, rk2, rk3, (uint4*)du,
                      (uint4*)dr, (uint4*)dz_out, C, n, ld, (const unsigned char*)mask);
-  SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_apply_mask_cn8");
+  SAR_LAUNCH_CHECK("sar_bn_add_relu_bwd_apply_cn8");
   return 0;
 }
 

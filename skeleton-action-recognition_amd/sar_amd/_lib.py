@@ -108,17 +108,11 @@ SIGNATURES = {
     "sar_data_bn_stats_f32": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp]),
     "sar_data_bn_apply_f32": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _i64, _fp]),
     "sar_data_bn_bwd_reduce_f32": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _i64, _fp, _fp, _fp]),
-    "sar_bn_add_relu_fwd_f32": (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_bwd_reduce_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_fwd_mask_f32": (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_bwd_reduce_mask_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_bwd_apply_mask_f32": (_i, [_fp] * 13 + [_i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_bwd_reduce_tail_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i64, _i64, C.POINTER(BnTail), _fp]),
-    "sar_bn_add_relu_bwd_apply_f32": (_i, [_fp] * 13 + [_i, _i64, _i64, _fp]),
-    "sar_affine2_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i64, _i64, _fp]),
-    "sar_affine2_amax_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_fwd_mask_amax_f32": (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_bwd_apply_mask_amax_f32": (_i, [_fp] * 15 + [_i, _i64, _i64, _fp]),
+    # block tail: optional pointers (mask, amax cells, tail) are None when unused (include/sar_hip.h)
+    "sar_bn_add_relu_fwd_f32": (_i, [_fp, _fp, _fp, _i] + [_fp] * 6 + [_i, _i64, _i64, _fp]),
+    "sar_bn_add_relu_bwd_reduce_f32": (_i, [_fp] * 8 + [_i, _i, _i64, _i64, C.POINTER(BnTail), _fp]),
+    "sar_bn_add_relu_bwd_apply_f32": (_i, [_fp] * 16 + [_i, _i64, _i64, _fp]),
+    "sar_affine2_f32": (_i, [_fp] * 7 + [_i, _i64, _i64, _fp]),
     "sar_pool_fwd_f32": (_i, [_fp, _i64, _i, _i, _i, _i, _fp, _fp]),
     "sar_fc_fwd_f32": (_i, [_fp, _fp, _fp, _i, _i, _i, _fp, _fp]),
     "sar_softmax_ce_f32": (_i, [_fp, _fp, _i, _i, _f, _fp, _fp, _fp, _fp]),
@@ -223,13 +217,9 @@ SIGNATURES = {
     "sar_conv_gemm_cn8": (_i, [C.POINTER(ConvDesc), _fp, _fp]),
     "sar_conv_wgrad_cn8_tile_frames": (_i, [_i]),
     "sar_conv_wgrad_cn8": (_i, [C.POINTER(WgradDesc), _i, _fp]),
-    "sar_bn_add_relu_fwd_cn8": (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_bwd_reduce_cn8": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_fwd_mask_cn8": (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_bwd_reduce_mask_cn8": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_bwd_apply_mask_cn8": (_i, [_fp] * 13 + [_i, _i64, _i64, _fp]),
-    "sar_bn_add_relu_bwd_reduce_tail_cn8": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i64, _i64, C.POINTER(BnTail), _fp]),
-    "sar_bn_add_relu_bwd_apply_cn8": (_i, [_fp] * 13 + [_i, _i64, _i64, _fp]),
+    "sar_bn_add_relu_fwd_cn8": (_i, [_fp, _fp, _fp, _i] + [_fp] * 5 + [_i, _i64, _i64, _fp]),
+    "sar_bn_add_relu_bwd_reduce_cn8": (_i, [_fp] * 8 + [_i, _i, _i64, _i64, C.POINTER(BnTail), _fp]),
+    "sar_bn_add_relu_bwd_apply_cn8": (_i, [_fp] * 14 + [_i, _i64, _i64, _fp]),
     "sar_affine2_cn8": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i64, _i64, _fp]),
     "sar_data_bn_apply_cn8": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _i64, _fp]),
     "sar_data_bn_bwd_reduce_cn8": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _i64, _fp, _fp, _fp]),

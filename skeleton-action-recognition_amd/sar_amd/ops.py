@@ -534,23 +534,10 @@ def relu_mask(u):
 
 
 def bn_add_relu_fwd(u, sc, sh, res_kind, r, rsc, rsh, y, mask=None, amax_cell=None):
-    """amax_cell: the bound cell of y (split arithmetic): raised by the pass itself when the masked kernel runs, else by a
-    separate sar_amax_f32 pass"""
-    if mask is not None and amax_cell is not None:
-        check(L.load().sar_bn_add_relu_fwd_mask_amax_f32(ptr(u), ptr(sc), ptr(sh), res_kind, ptr(r), ptr(rsc), ptr(rsh), ptr(y), ptr(mask),
-                                                         ptr(amax_cell), u.shape[0], u.shape[1], u.stride(0), stream_ptr()),
-              "sar_bn_add_relu_fwd_mask_amax_f32")
-        return
-    if amax_cell is not None:
-        bn_add_relu_fwd(u, sc, sh, res_kind, r, rsc, rsh, y, mask)
-        amax(y, amax_cell)
-        return
-    if mask is not None:
-        check(L.load().sar_bn_add_relu_fwd_mask_f32(ptr(u), ptr(sc), ptr(sh), res_kind, ptr(r), ptr(rsc), ptr(rsh), ptr(y), ptr(mask),
-                                                    u.shape[0], u.shape[1], u.stride(0), stream_ptr()), "sar_bn_add_relu_fwd_mask_f32")
-        return
-    check(L.load().sar_bn_add_relu_fwd_f32(ptr(u), ptr(sc), ptr(sh), res_kind, ptr(r), ptr(rsc), ptr(rsh), ptr(y),
-                                           u.shape[0], u.shape[1], u.stride(0), stream_ptr()), "sar_bn_add_relu_fwd_f32")
+    """mask (relu_mask): written beside y.  amax_cell: the bound cell of y (split arithmetic), raised by the pass itself"""
+    check(L.load().sar_bn_add_relu_fwd_f32(ptr(u), ptr(sc), ptr(sh), res_kind, ptr(r), ptr(rsc), ptr(rsh), ptr(y), ptr(mask),
+                                           ptr(amax_cell), u.shape[0], u.shape[1], u.stride(0), stream_ptr()),
+          "sar_bn_add_relu_fwd_f32")
 
 
 _REDUCE_CHUNK = int(os.environ.get("SAR_BWD_REDUCE_CHUNK", "8192"))      # row elements per workgroup of the BN-backward reductions
@@ -591,18 +578,12 @@ def bn_add_relu_bwd_reduce(dy, y, u, r, mu=None, mr=None, tail=None, mask=None):
     Cc, n = u.shape
     nparts = max(1, min(4096, (n + _REDUCE_CHUNK - 1) // _REDUCE_CHUNK))
     partials = torch.empty((Cc, nparts, 4), dtype=torch.float32, device=u.device)
-    if mask is not None and tail is None:
-        check(L.load().sar_bn_add_relu_bwd_reduce_mask_f32(ptr(dy), ptr(mask), ptr(u), ptr(r), ptr(mu), ptr(mr), ptr(partials), nparts,
-                                                           Cc, n, u.stride(0), stream_ptr()), "sar_bn_add_relu_bwd_reduce_mask_f32")
-        return partials, nparts
-    if tail is not None:
-        assert Cc <= 4096
-        check(L.load().sar_bn_add_relu_bwd_reduce_tail_f32(ptr(dy), ptr(y), ptr(u), ptr(r), ptr(mu), ptr(mr), ptr(partials), nparts, Cc,
-                                                           n, u.stride(0), C.byref(tail), stream_ptr()),
-              "sar_bn_add_relu_bwd_reduce_tail_f32")
-        return partials, nparts
-    check(L.load().sar_bn_add_relu_bwd_reduce_f32(ptr(dy), ptr(y), ptr(u), ptr(r), ptr(mu), ptr(mr), ptr(partials), nparts, Cc, n,
-                                                  u.stride(0), stream_ptr()), "sar_bn_add_relu_bwd_reduce_f32")
+    assert tail is None or Cc <= 4096        # bn_tail_tickets
+    # with a tail the pass keeps reading y, as it always has: the mask is passed only without one
+    check(L.load().sar_bn_add_relu_bwd_reduce_f32(ptr(dy), ptr(y), ptr(mask if tail is None else None), ptr(u), ptr(r), ptr(mu), ptr(mr),
+                                                  ptr(partials), nparts, Cc, n, u.stride(0),
+                                                  C.byref(tail) if tail is not None else None, stream_ptr()),
+          "sar_bn_add_relu_bwd_reduce_f32")
     return partials, nparts
 
 
@@ -611,37 +592,15 @@ def bn_add_relu_bwd_apply(dy, y, u, r, k, rk, du, dr, dz_out, mask=None, amax_ce
     residual branch's dense 1x1 data gradient)"""
     Cc, n = u.shape
     rk = rk or (None, None, None)
-    if mask is not None and amax_cell is not None:
-        check(L.load().sar_bn_add_relu_bwd_apply_mask_amax_f32(ptr(dy), ptr(mask), ptr(u), ptr(r), ptr(k[0]), ptr(k[1]), ptr(k[2]),
-                                                               ptr(rk[0]), ptr(rk[1]), ptr(rk[2]), ptr(du), ptr(dr), ptr(dz_out),
-                                                               ptr(amax_cell), ptr(amax_dr_cell if dr is not None else None),
-                                                               Cc, n, u.stride(0), stream_ptr()),
-              "sar_bn_add_relu_bwd_apply_mask_amax_f32")
-        return
-    if amax_cell is not None or amax_dr_cell is not None:
-        bn_add_relu_bwd_apply(dy, y, u, r, k, rk, du, dr, dz_out, mask)
-        if amax_cell is not None:
-            amax(du, amax_cell)
-        if amax_dr_cell is not None and dr is not None:
-            amax(dr, amax_dr_cell)
-        return
-    if mask is not None:
-        check(L.load().sar_bn_add_relu_bwd_apply_mask_f32(ptr(dy), ptr(mask), ptr(u), ptr(r), ptr(k[0]), ptr(k[1]), ptr(k[2]),
-                                                          ptr(rk[0]), ptr(rk[1]), ptr(rk[2]), ptr(du), ptr(dr), ptr(dz_out), Cc, n,
-                                                          u.stride(0), stream_ptr()), "sar_bn_add_relu_bwd_apply_mask_f32")
-        return
-    check(L.load().sar_bn_add_relu_bwd_apply_f32(ptr(dy), ptr(y), ptr(u), ptr(r), ptr(k[0]), ptr(k[1]), ptr(k[2]),
-                                                 ptr(rk[0]), ptr(rk[1]), ptr(rk[2]), ptr(du), ptr(dr), ptr(dz_out), Cc, n,
-                                                 u.stride(0), stream_ptr()), "sar_bn_add_relu_bwd_apply_f32")
+    check(L.load().sar_bn_add_relu_bwd_apply_f32(ptr(dy), ptr(y), ptr(mask), ptr(u), ptr(r), ptr(k[0]), ptr(k[1]), ptr(k[2]),
+                                                 ptr(rk[0]), ptr(rk[1]), ptr(rk[2]), ptr(du), ptr(dr), ptr(dz_out), ptr(amax_cell),
+                                                 ptr(amax_dr_cell if dr is not None else None), Cc, n, u.stride(0), stream_ptr()),
+          "sar_bn_add_relu_bwd_apply_f32")
 
 
 def affine2(a, b, k, out, amax_cell=None):
     Cc, n = a.shape
-    if amax_cell is not None:
-        check(L.load().sar_affine2_amax_f32(ptr(a), ptr(b), ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(out), ptr(amax_cell), Cc, n, a.stride(0),
-                                            stream_ptr()), "sar_affine2_amax_f32")
-        return
-    check(L.load().sar_affine2_f32(ptr(a), ptr(b), ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(out), Cc, n, a.stride(0),
+    check(L.load().sar_affine2_f32(ptr(a), ptr(b), ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(out), ptr(amax_cell), Cc, n, a.stride(0),
                                    stream_ptr()), "sar_affine2_f32")
 
 

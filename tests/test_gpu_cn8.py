@@ -191,7 +191,7 @@ def test_graph_conv_data_gradient(dev, B, cin, f, T):
 
 @pytest.mark.parametrize("C,n,kind", [(64, 5000, 1), (128, 3001, 2), (20, 777, 0), (256, 9375, 2)])
 def test_block_tail_relu_mask_is_bit_identical(dev, C, n, kind):
-    """sar_bn_add_relu_fwd_mask_cn8 / _bwd_reduce_mask_cn8 / _bwd_apply_mask_cn8: the forward tail's one-byte-per-unit ReLU mask
+    """sar_bn_add_relu_fwd_cn8 / _bwd_reduce_cn8 / _bwd_apply_cn8 with a mask: the forward tail's one-byte-per-unit ReLU mask
     (bit j = stored channel 8 g + j > 0) replaces the reads of y in both backward passes -- every output bit for bit equal to
     the y-reading kernels, and the mask equal to its definition."""
     from sar_amd import ops8

@@ -642,7 +642,7 @@ def tail_case(C, n):
 @pytest.mark.parametrize("kind", [0, 1, 2])
 @pytest.mark.parametrize("C,n", TAIL_SHAPES)
 def test_block_tail_forward(dev, C, n, kind, pad):
-    """sar_bn_add_relu_fwd_cn8 and _mask_cn8: bit-equal outputs, the mask equal to its definition on the stored y"""
+    """sar_bn_add_relu_fwd_cn8 without and with a mask: bit-equal outputs, the mask equal to its definition on the stored y"""
     from sar_amd import ops8
     c = tail_case(C, n)
     d = lambda t: t.to(dev)
@@ -662,7 +662,7 @@ def test_block_tail_forward(dev, C, n, kind, pad):
 @pytest.mark.parametrize("pad", PADS)
 @pytest.mark.parametrize("C,n", TAIL_SHAPES)
 def test_block_tail_backward_reduce(dev, C, n, pad):
-    """sar_bn_add_relu_bwd_reduce_cn8, _mask_cn8 and _tail_cn8: partials (sum dz, sum dz (u - mu), sum dz (r - mr)), dz = dy where the
+    """sar_bn_add_relu_bwd_reduce_cn8, plain, with a mask and with a tail: partials (sum dz, sum dz (u - mu), sum dz (r - mr)), dz = dy where the
     stored y > 0.  The folded finalisation against sar_bn_bwd_finalize_f32 on the plain partials: the same sums in another order, 1e-6
     (tests/test_gpu_guard_bands.py's bar for it); the ticket array is back to zero."""
     from sar_amd import ops, ops8
@@ -711,7 +711,7 @@ def test_block_tail_backward_reduce(dev, C, n, pad):
 @pytest.mark.parametrize("pad", PADS)
 @pytest.mark.parametrize("C,n", TAIL_SHAPES)
 def test_block_tail_backward_apply_and_affine2(dev, C, n, pad):
-    """sar_bn_add_relu_bwd_apply_cn8 / _mask_cn8: du = k1 dz + k2 u + k3, dr = rk1 dz + rk2 r + rk3, dz_out = dz (bitwise: a copy
+    """sar_bn_add_relu_bwd_apply_cn8 without / with a mask: du = k1 dz + k2 u + k3, dr = rk1 dz + rk2 r + rk3, dz_out = dz (bitwise: a copy
     or a zero); sar_affine2_cn8: out = k1 a + k2 b + k3"""
     from sar_amd import ops8
     c = tail_case(C, n)

@@ -344,7 +344,7 @@ def tail_case(C, n):
 @pytest.mark.parametrize("kind", [1, 2])
 @pytest.mark.parametrize("C,n", TAIL_SHAPES)
 def test_block_tail_forward(dev, C, n, kind, pad):
-    """sar_bn_add_relu_fwd_f32 and _mask_f32: y = relu(u sc + sh + residual).  The mask exists only for rows of 4-element groups
+    """sar_bn_add_relu_fwd_f32 without and with a mask: y = relu(u sc + sh + residual).  The mask exists only for rows of 4-element groups
     (ops.relu_mask: n % 4 == 0 and ld % 4 == 0), else relu_mask returns None and the masked kernel rejects the rows."""
     from sar_amd import ops
     c = tail_case(C, n)
@@ -376,7 +376,7 @@ def test_block_tail_forward(dev, C, n, kind, pad):
 @pytest.mark.parametrize("pad", PADS)
 @pytest.mark.parametrize("C,n", TAIL_SHAPES)
 def test_block_tail_backward_reduce(dev, C, n, pad):
-    """sar_bn_add_relu_bwd_reduce_f32, _mask_f32 and _tail_f32: partials (sum dz, sum dz (u - mu), sum dz (r - mr)), dz = dy where y > 0"""
+    """sar_bn_add_relu_bwd_reduce_f32, plain, with a mask and with a tail: partials (sum dz, sum dz (u - mu), sum dz (r - mr)), dz = dy where y > 0"""
     from sar_amd import ops
     from sar_amd.stgcn import _BN
     c = tail_case(C, n)
@@ -426,7 +426,7 @@ def test_block_tail_backward_reduce(dev, C, n, pad):
 @pytest.mark.parametrize("pad", PADS)
 @pytest.mark.parametrize("C,n", TAIL_SHAPES)
 def test_block_tail_backward_apply_and_affine2(dev, C, n, pad):
-    """sar_bn_add_relu_bwd_apply_f32 / _mask_f32: du = k1 dz + k2 u + k3, dr = rk1 dz + rk2 r + rk3, dz_out = dz; sar_affine2_f32:
+    """sar_bn_add_relu_bwd_apply_f32 without / with a mask: du = k1 dz + k2 u + k3, dr = rk1 dz + rk2 r + rk3, dz_out = dz; sar_affine2_f32:
     out = k1 a + k2 b + k3 (1e-6: one fused multiply-add chain per element, test_gpu_stgin.py's bar for such kernels)"""
     from sar_amd import ops
     c = tail_case(C, n)

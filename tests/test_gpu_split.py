@@ -227,7 +227,7 @@ def test_a_diverged_step_is_visible_in_the_split_engine(dev):
 
 
 def test_block_tail_backward_raises_the_bounds_of_du_and_dr(dev):
-    """sar_bn_add_relu_bwd_apply_mask_amax_f32 raises amax_du AND (round 6) amax_dr to the largest magnitude it wrote -- what a
+    """sar_bn_add_relu_bwd_apply_f32 (with a mask) raises amax_du AND (round 6) amax_dr to the largest magnitude it wrote -- what a
     separate sar_amax_f32 pass over each tensor gives -- and the outputs do not depend on the cells being asked for"""
     from sar_amd import ops
     g = torch.Generator().manual_seed(5)
@@ -251,6 +251,76 @@ def test_block_tail_backward_raises_the_bounds_of_du_and_dr(dev):
     ops.bn_add_relu_bwd_apply(dy, y, u, None, k, None, du2, None, None, mask=mask, amax_cell=only_du, amax_dr_cell=cells[1:2])
     torch.cuda.synchronize()
     assert only_du.item() == _bits(du2.abs().max().item()) and cells[1].item() == _bits(dr.abs().max().item())
+
+
+@pytest.mark.parametrize("n,ld", [(5, 7), (8, 12)])
+def test_amax_by_products_without_a_mask(dev, monkeypatch, n, ld):
+    """the amax cells of sar_bn_add_relu_fwd_f32, sar_bn_add_relu_bwd_apply_f32 and sar_affine2_f32 WITHOUT a mask: rows that are no
+    float4 groups (n = 5, ld = 7: the scalar kernels) and float4 rows with the mask switched off (n = 8, ld = 12, SAR_RELU_MASK=0:
+    the float4 kernels).  Each cell ends as exactly the largest bits(|x|) over the live elements of the tensor the same call wrote
+    (read back), is only ever raised, and never sees the margins [n, ld), which hold a huge finite value in every operand"""
+    from sar_amd import ops
+    monkeypatch.setattr(ops, "RELU_MASK", False)
+    C, HUGE, ABOVE = 3, 3e38, 1e30
+    g = torch.Generator().manual_seed(11 + n)
+
+    def rows(live=None):
+        buf = torch.full((C, ld), HUGE, device=dev)
+        if live is not None:
+            buf[:, :n] = live.to(dev)
+        return buf[:, :n]
+
+    def rand():
+        return rows(torch.randn(C, n, generator=g))
+
+    def vecs(k):
+        return [torch.randn(C, generator=g).to(dev) for _ in range(k)]
+
+    def check(run, ncells):
+        """run(cells) launches the pass into fresh outputs and returns the tensors that cells[0], cells[1].. bound; a cell without
+        a tensor must be left alone"""
+        for seed in (0, _bits(ABOVE)):
+            cells = torch.full((ncells,), seed, dtype=torch.int32, device=dev)
+            outs = run(cells)
+            torch.cuda.synchronize()
+            got = cells.cpu().tolist()
+            for i in range(ncells):
+                if i >= len(outs):
+                    assert got[i] == seed
+                    continue
+                top = outs[i].cpu().abs().max().item()
+                assert 0 < top < ABOVE
+                assert got[i] == (_bits(top) if seed == 0 else seed), (i, seed, got[i], _bits(top))
+
+    u, r, dy, y = rand(), rand(), rand(), rand()
+    assert ops.relu_mask(u) is None
+    sc, sh, rsc, rsh = vecs(4)
+    for res_kind in (0, 2):
+        def fwd(cells):
+            out = rows()
+            ops.bn_add_relu_fwd(u, sc, sh, res_kind, r if res_kind else None, rsc if res_kind else None, rsh if res_kind else None,
+                                out, mask=ops.relu_mask(u), amax_cell=cells)
+            return [out]
+        check(fwd, 1)
+    k, rk = vecs(3), vecs(3)
+
+    def apply_with_dr(cells):
+        du, dr = rows(), rows()
+        ops.bn_add_relu_bwd_apply(dy, y, u, r, k, rk, du, dr, None, amax_cell=cells[0:1], amax_dr_cell=cells[1:2])
+        return [du, dr]
+
+    def apply_without_dr(cells):
+        du = rows()
+        ops.bn_add_relu_bwd_apply(dy, y, u, None, k, None, du, None, None, amax_cell=cells[0:1], amax_dr_cell=cells[1:2])
+        return [du]
+
+    def affine2(cells):
+        out = rows()
+        ops.affine2(dy, u, k, out, amax_cell=cells)
+        return [out]
+    check(apply_with_dr, 2)
+    check(apply_without_dr, 2)
+    check(affine2, 1)
 
 
 @pytest.mark.parametrize("arith", ARITHS)

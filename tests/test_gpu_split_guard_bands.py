@@ -783,8 +783,8 @@ def test_amax_of_a_padded_view(dev, C, n, pad):
 @pytest.mark.parametrize("pad", PADS)
 @pytest.mark.parametrize("C,n", TAIL_SHAPES)
 def test_block_tail_bound_cells(dev, C, n, pad):
-    """the amax_cell / amax_dr_cell by-products of bn_add_relu_fwd (with the mask where rows are 4-element groups: the fused kernel;
-    else the separate pass), bn_add_relu_bwd_apply and affine2: each cell holds the bits of max |live output| -- the same as the
+    """the amax_cell / amax_dr_cell by-products of bn_add_relu_fwd (with the mask where rows are 4-element groups, without
+    one elsewhere: the pass itself raises the cell either way), bn_add_relu_bwd_apply and affine2: each cell holds the bits of max |live output| -- the same as the
     tight launch's, since the outputs are -- and the outputs do not depend on the cell being asked for"""
     from sar_amd import ops
     c = tail_case(C, n)

@@ -140,7 +140,7 @@ def test_graph_conv_gradients(dev, B, cin, f, T):
 @pytest.mark.parametrize("B,cin,f,T", [(2, 64, 64, 12), (2, 64, 128, 8), (1, 128, 256, 4), (4, 256, 256, 76), (2, 40, 72, 8)])
 def test_graph_data_gradient_gated_epilogue_f32(dev, B, cin, f, T):
     """SAR_EPI_ADD_GATE of sar_conv_gemm_f32 (include/sar_hip.h): out = gate(W^T dg . A^T + aux) with the ReLU-mask bytes of the
-    block below (one bit per column, sar_bn_add_relu_fwd_mask_f32's layout), partials = (sum out, sum out (aux2 - mean)): the
+    block below (one bit per column, the mask layout of sar_bn_add_relu_fwd_f32), partials = (sum out, sum out (aux2 - mean)): the
     stored tensor equals the SAR_EPI_ADD result gated afterwards bit for bit, the sums equal fp64 sums of it to 1e-6."""
     from sar_amd import ops, _lib as L
     g = torch.Generator().manual_seed(11 * cin + f)
@@ -273,7 +273,7 @@ def test_residual_conv_gradients(dev, B, cin, f, T, s):
 
 @pytest.mark.parametrize("C,n,res", [(64, 2 * 300 * 25, True), (128, 40000, False), (20, 777, True), (256, 9375 * 4, True)])
 def test_folded_bn_backward_finalisation(dev, C, n, res):
-    """sar_bn_add_relu_bwd_reduce_tail_f32 / _cn8 (the reduce kernel's last workgroup per channel finalises: dgamma, dbeta,
+    """sar_bn_add_relu_bwd_reduce_f32 / _cn8 with a tail (the reduce kernel's last workgroup per channel finalises: dgamma, dbeta,
     k1..k3 of the block's BatchNorm and of the residual branch's) against the separate sar_bn_bwd_finalize_f32 launches on the
     same partials -- the same fp64 sums in another order: equal to 1e-6 -- run several times (the ticket array must come back
     to zero; a stale partial would show as a wrong coefficient)."""
@@ -319,7 +319,7 @@ def test_folded_bn_backward_finalisation(dev, C, n, res):
 
 @pytest.mark.parametrize("C,n,kind", [(64, 5000, 1), (128, 3000, 2), (20, 776, 0), (256, 9376, 2)])
 def test_block_tail_relu_mask_is_bit_identical_f32(dev, C, n, kind):
-    """sar_bn_add_relu_{fwd,bwd_reduce,bwd_apply}_mask_f32: one byte per float4 of y written by the forward tail, read by both
+    """sar_bn_add_relu_{fwd,bwd_reduce,bwd_apply}_f32 with a mask: one byte per float4 of y written by the forward tail, read by both
     backward passes instead of y -- every output bit for bit equal to the y-reading kernels, the mask equal to its definition."""
     from sar_amd import ops
     g = torch.Generator().manual_seed(3 * C + n)

@@ -138,7 +138,7 @@ def assert_flat_guards_untouched(whole, n, fill, k=8, what=""):
 # runs the split-arithmetic kernels through the same ones)
 
 def mask_bytes(keep):
-    """(C, n) bool -> (C, n / 4) bytes, bit j = element 4 i + j (sar_bn_add_relu_fwd_mask_f32's layout)"""
+    """(C, n) bool -> (C, n / 4) bytes, bit j = element 4 i + j (the mask layout of sar_bn_add_relu_fwd_f32)"""
     C, n = keep.shape
     return (keep.view(C, n // 4, 4).to(torch.int32) * torch.tensor([1, 2, 4, 8], dtype=torch.int32, device=keep.device)).sum(dim=2).to(torch.uint8)
 
@@ -361,7 +361,7 @@ def guarded_cn8_mask(src_or_shape, pad, dev, front=2, back=2):
 
 
 def cn8_mask_bytes(keep):
-    """(C, n) bool -> (ceil(C/8), n) bytes, bit j of byte (g, col) = channel 8 g + j (sar_bn_add_relu_fwd_mask_cn8's layout)"""
+    """(C, n) bool -> (ceil(C/8), n) bytes, bit j of byte (g, col) = channel 8 g + j (the mask layout of sar_bn_add_relu_fwd_cn8)"""
     C, n = keep.shape
     G = (C + 7) // 8
     kb = torch.zeros(G * 8, n, dtype=torch.int32)
