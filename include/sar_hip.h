@@ -317,6 +317,21 @@ int sar_data_bn_apply_f32(const float* x, int N, int C, int T, int V, int M, con
 /* backward: partials [V*C][N][2] = (sum dy, sum dy*(x_raw - mean[ch])) from dy in CN layout (mean may be NULL). */
 int sar_data_bn_bwd_reduce_f32(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent, int motion,
                                const float* dy, int64_t ld_dy, const float* mean, float* partials, sar_stream_t s);
+/* backward apply: dx (N,C,T,V,M) = d loss / d x from dy = d loss / d data_bn(x) in CN layout and the coefficients k1..k3 [V*C] that
+ * sar_bn_bwd_finalize_f32 emits (in terms of the raw value).  With val the value the forward pass normalised (recomputed from x by
+ * the same float32 operations), ch = v*C+c:
+ *   dval[n,c,t,v,m] = k1[ch]*dy[c][((n*M+m)*T+t)*V+v] + k2[ch]*val[n,c,t,v,m] + k3[ch]
+ *   motion == 0: df = dval;   motion != 0: df[t] = (t >= 1 ? dval[t-1] : 0) - (t <= T-2 ? dval[t] : 0)   (T = 1: dx == 0)
+ *   no table:    dx = df;     table: dx[u] = df[u] - sum over v != u with bone_parent[v] == u of df[v], v ascending; a self-pair
+ *                             (bone_parent[u] == u, val == 0) forms neither of its two terms and so contributes exactly 0.
+ * Gather form: every dx element is written once by one thread, its terms added in that fixed order (no atomics; bitwise reproducible).
+ * Limits of the other data_bn entry points (V*M <= 256).  bone_parent is DEVICE memory, the table the forward pass read: its entries
+ * (-1 .. V-1) cannot be checked here without a read-back; sar_amd.stgcn checks the pairs when it builds the table. */
+int sar_data_bn_bwd_apply_f32(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent, int motion,
+                              const float* dy, int64_t ld_dy, const float* k1, const float* k2, const float* k3,
+                              float* dx /* (N,C,T,V,M) contiguous */, sar_stream_t s);
+/* frames of dx per workgroup of the two backward apply kernels (tests place a chunk boundary with it) */
+int sar_data_bn_dx_frames(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Block tail, models/stgcn.py:37,62-63 and models/resnet18.py:46-63, and its gradient: one entry point per pass.  An optional
@@ -883,6 +898,11 @@ int sar_data_bn_apply_cn8(const float* x, int N, int C, int T, int V, int M, con
                           const float* scale, const float* shift, void* out, int64_t ld_out, sar_stream_t s);
 int sar_data_bn_bwd_reduce_cn8(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent, int motion,
                                const void* dy, int64_t ld_dy, const float* mean, float* partials, sar_stream_t s);
+/* backward apply (sar_data_bn_bwd_apply_f32: the same formulas, order of terms and limits, and C <= 8): dy = the CN8 plane that
+ * sar_data_bn_bwd_reduce_cn8 reads (bf16 -> float32 is exact); dx is float32 (N,C,T,V,M) */
+int sar_data_bn_bwd_apply_cn8(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent, int motion,
+                              const void* dy, int64_t ld_dy, const float* k1, const float* k2, const float* k3,
+                              float* dx /* (N,C,T,V,M) contiguous */, sar_stream_t s);
 /* GlobalAveragePooling2D + mean over bodies (models/stgcn.py:153-156) on a CN8 tensor, and its gradient */
 int sar_pool_fwd_cn8(const void* y, int64_t ld, int C, int B, int TV, int Mp, float* feat, sar_stream_t s);
 int sar_pool_bwd_cn8(const float* dfeat, int64_t ld, int C, int B, int TV, int Mp, void* dy, sar_stream_t s);

@@ -343,6 +343,97 @@ __global__ __launch_bounds__(TPB) void data_bn_apply_cn8_kernel(const float* __r
   }
 }
 
+// Backward apply pass of data_bn: d loss / d x in the clip layout, from dy = d loss / d data_bn(x) and the coefficients of
+// bn_bwd_finalize_kernel (include/sar_hip.h has the formulas).  Workgroup = (n, c, chunk of DX_FRAMES frames), gather form, three
+// phases in LDS: (0) the x frames the chunk needs (one coalesced read; with the motion transform one halo frame on either side),
+// the channel's coefficients and the bone table with the children lists of its joints; (1) dval = k1 * dy + k2 * val + k3 of the
+// chunk's frames -- with motion one halo frame in front, since frame t of dx reads dval of t - 1 and t --, val being load_joint()
+// on the staged frames, i.e. the forward pass's own float32 operations; (2) every thread writes the dx elements it owns, the
+// terms in a fixed order.  No element is written twice and nothing is accumulated across threads: the result does not depend on
+// the grid.
+constexpr int DX_FRAMES = 16;
+
+template <bool DY_CN8>
+__global__ __launch_bounds__(TPB) void data_bn_bwd_apply_kernel(const float* __restrict__ x, int C, int T, int V, int M,
+                                                                const int* __restrict__ bone_parent, int motion,
+                                                                const float* __restrict__ dy, int64_t ld_dy,
+                                                                const float* __restrict__ k1, const float* __restrict__ k2,
+                                                                const float* __restrict__ k3, float* __restrict__ dx,
+                                                                int nchunks) {
+  extern __shared__ float dx_lds[];     // (2 * DX_FRAMES + 3) * V * M + 6 * V + 1 words
+  const int sl = blockIdx.x / nchunks, chunk = blockIdx.x - sl * nchunks;
+  const int n = sl / C, c = sl - n * C;
+  const int VM = V * M;
+  const float* slab = x + (int64_t)sl * T * VM;
+  const int t0 = chunk * DX_FRAMES, t1 = (t0 + DX_FRAMES < T) ? t0 + DX_FRAMES : T;
+  const int halo = motion ? 1 : 0;
+  float* xs = dx_lds;                                 // x[DX_FRAMES + 2][V * M]: row 0 is frame tx0
+  float* dval = xs + (DX_FRAMES + 2) * VM;            // dval[DX_FRAMES + 1][V * M]: row 0 is frame tx0
+  float* kk = dval + (DX_FRAMES + 1) * VM;            // k1, k2, k3 of channels (v, c): [3][V]
+  int* par = reinterpret_cast<int*>(kk + 3 * V);      // the bone table [V]
+  int* cbeg = par + V;                                // the children of joint u (self-pair excluded), ascending:
+  int* clist = cbeg + V + 1;                          //   clist[cbeg[u] .. cbeg[u + 1])
+  const int tx0 = t0 - halo;
+  const int xrows = t1 - t0 + 2 * halo;               // frames tx0 .. t1 - 1 + halo, those inside the clip
+  for (int e = threadIdx.x; e < xrows * VM; e += TPB) {
+    const int i = tx0 * VM + e;
+    if (i >= 0 && i < T * VM) xs[e] = slab[i];
+  }
+  for (int v = threadIdx.x; v < V; v += TPB) {
+    kk[v] = k1[v * C + c];
+    kk[V + v] = k2[v * C + c];
+    kk[2 * V + v] = k3[v * C + c];
+    if (bone_parent) par[v] = bone_parent[v];
+  }
+  __syncthreads();
+  if (bone_parent)
+    for (int u = threadIdx.x; u < V; u += TPB) {
+      int beg = 0;                                    // children of the joints below u come first
+      for (int v = 0; v < V; ++v) beg += (par[v] >= 0 && par[v] < u && par[v] != v) ? 1 : 0;
+      int w = beg;
+      for (int v = 0; v < V; ++v)
+        if (par[v] == u && v != u) clist[w++] = v;
+      cbeg[u] = beg;
+      if (u == V - 1) cbeg[V] = w;
+    }
+  const int staged = (t1 - t0 + halo) * VM;
+  for (int e = threadIdx.x; e < staged; e += TPB) {
+    const int row = e / VM, r = e - row * VM;
+    const int v = r / M, m = r - v * M, t = tx0 + row;
+    float d = 0.f;      // frame -1 does not exist; the motion value of frame T - 1 is the constant 0: its dval reaches nothing
+    if (t >= 0 && !(motion && t >= T - 1)) {
+      // frames relative to tx0: the staged rows are the slab, T - tx0 its length
+      const float val = load_joint(xs, row, v, m, V, M, bone_parent ? par : nullptr, motion, T - tx0);
+      const int64_t pos = ((int64_t)(n * M + m) * T + t) * V + v;
+      float g;
+      if (DY_CN8) g = __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(dy)[pos * 8 + c] << 16);
+      else g = dy[(int64_t)c * ld_dy + pos];
+      d = fmaf(kk[v], g, fmaf(kk[V + v], val, kk[2 * V + v]));
+    }
+    dval[e] = d;
+  }
+  __syncthreads();
+  float* out = dx + (int64_t)sl * T * VM + (int64_t)t0 * VM;
+  const int owned = (t1 - t0) * VM;
+  for (int e = threadIdx.x; e < owned; e += TPB) {
+    const int row = e / VM, r = e - row * VM;
+    const int u = r / M, m = r - u * M;
+    const float* cur = dval + (row + halo) * VM + m;      // dval of frame t, joint 0, body m
+    // adjoint of the motion transform: val[t - 1] = f[t] - f[t - 1] and val[t] = f[t + 1] - f[t] read frame t of f
+    auto df = [&](int v) { return motion ? cur[v * M - VM] - cur[v * M] : cur[v * M]; };
+    float acc;
+    if (!bone_parent) {
+      acc = df(u);
+    } else {
+      // adjoint of the bone transform f[v] = x[v] - x[parent[v]]: own term, minus the children in ascending order.  A self-pair
+      // (parent[u] == u) has f[u] = x[u] - x[u]: neither of its two terms is formed, so that it contributes exactly 0
+      acc = par[u] == u ? 0.f : df(u);
+      for (int i = cbeg[u]; i < cbeg[u + 1]; ++i) acc -= df(clist[i]);
+    }
+    out[e] = acc;
+  }
+}
+
 // ------------------------------------------------------------------------------------ row-wise kernels
 template <int VEC> struct VecT;
 template <> struct VecT<4> { typedef float4 T; };
@@ -822,6 +913,49 @@ extern "C" int sar_data_bn_bwd_reduce_cn8(const float* x, int N, int C, int T, i
   hipLaunchKernelGGL((data_bn_reduce_kernel<true, true>), dim3(N * C), dim3(TPB), 0, as_stream(s), x, N, C, T, V, M, bone_parent,
                      motion, (const float*)dy, ld_dy, mean, partials);
   SAR_LAUNCH_CHECK("sar_data_bn_bwd_reduce_cn8");
+  return 0;
+}
+
+extern "C" int sar_data_bn_dx_frames(void) { return DX_FRAMES; }
+
+// every check of the two backward apply entry points, before anything is launched; *nchunks: frame chunks per (n, c) slab
+static int data_bn_bwd_apply_check(const char* fn, const float* x, int N, int C, int T, int V, int M, const void* dy, int64_t ld_dy,
+                                   const float* k1, const float* k2, const float* k3, const float* dx, int cmax, int* nchunks) {
+  SAR_REQUIRE(x && dy && k1 && k2 && k3 && dx, "%s: null operand", fn);
+  SAR_REQUIRE(N > 0 && C > 0 && T > 0 && V > 0 && M > 0, "%s: bad sizes (N %d, C %d, T %d, V %d, M %d)", fn, N, C, T, V, M);
+  SAR_REQUIRE(V * (int64_t)M <= TPB, "%s: V*M = %lld exceeds %d", fn, (long long)V * M, TPB);
+  SAR_REQUIRE(C <= cmax, "%s: C = %d exceeds %d", fn, C, cmax);
+  SAR_REQUIRE((int64_t)T * V * M <= INT32_MAX, "%s: a slab of T*V*M = %lld elements", fn, (long long)T * V * M);
+  SAR_REQUIRE(ld_dy >= (int64_t)N * M * T * V, "%s: ld_dy = %lld is less than N*M*T*V = %lld", fn, (long long)ld_dy,
+              (long long)N * M * T * V);
+  *nchunks = (T + DX_FRAMES - 1) / DX_FRAMES;
+  SAR_REQUIRE((int64_t)N * C * *nchunks <= INT32_MAX, "%s: N*C*chunks = %lld workgroups", fn, (long long)N * C * *nchunks);
+  return 0;
+}
+
+extern "C" int sar_data_bn_bwd_apply_f32(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent, int motion,
+                                         const float* dy, int64_t ld_dy, const float* k1, const float* k2, const float* k3, float* dx,
+                                         sar_stream_t s) {
+  int nchunks = 0;
+  int rc = data_bn_bwd_apply_check("sar_data_bn_bwd_apply_f32", x, N, C, T, V, M, dy, ld_dy, k1, k2, k3, dx, INT32_MAX, &nchunks);
+  if (rc) return rc;
+  const size_t lds = ((size_t)(2 * DX_FRAMES + 3) * V * M + 6 * V + 1) * sizeof(float);
+  hipLaunchKernelGGL(data_bn_bwd_apply_kernel<false>, dim3(N * C * nchunks), dim3(TPB), lds, as_stream(s), x, C, T, V, M, bone_parent,
+                     motion, dy, ld_dy, k1, k2, k3, dx, nchunks);
+  SAR_LAUNCH_CHECK("sar_data_bn_bwd_apply_f32");
+  return 0;
+}
+
+extern "C" int sar_data_bn_bwd_apply_cn8(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent, int motion,
+                                         const void* dy, int64_t ld_dy, const float* k1, const float* k2, const float* k3, float* dx,
+                                         sar_stream_t s) {
+  int nchunks = 0;
+  int rc = data_bn_bwd_apply_check("sar_data_bn_bwd_apply_cn8", x, N, C, T, V, M, dy, ld_dy, k1, k2, k3, dx, 8, &nchunks);
+  if (rc) return rc;
+  const size_t lds = ((size_t)(2 * DX_FRAMES + 3) * V * M + 6 * V + 1) * sizeof(float);
+  hipLaunchKernelGGL(data_bn_bwd_apply_kernel<true>, dim3(N * C * nchunks), dim3(TPB), lds, as_stream(s), x, C, T, V, M, bone_parent,
+                     motion, (const float*)dy, ld_dy, k1, k2, k3, dx, nchunks);
+  SAR_LAUNCH_CHECK("sar_data_bn_bwd_apply_cn8");
   return 0;
 }
 

@@ -35,7 +35,8 @@ Indices carry no gradient.  Under torch.no_grad(), or when nothing requires a gr
 Limits (ValueError before any launch): x a contiguous float32 CUDA (N, C, T, V) tensor, top_k <= T <= 2048, every width <= 128,
 T N < 2^22 (the 1x1 products' column limit).
 
-Not wired into main_gnn.py or the engines: their data_bn prologue returns no input gradient."""
+Not wired into main_gnn.py (the reference wires it into no model).  In front of a whole-network model (models.stgcn.Model and its
+siblings) the scorer trains: the engines return d loss / d clip (INTEGRATION.md has the example)."""
 import math
 
 import torch

@@ -36,9 +36,10 @@ class _STGCNFunction(torch.autograd.Function):
         eng = ctx.engine
         if not ctx.training:
             raise RuntimeError("backward through model(x, training=False) is not supported (inference path)")
-        eng.backward(dlogits.contiguous())
+        # d loss / d x only when x asks for it (a leaf with requires_grad, or a learned front end such as TemporalSampler)
+        dx = eng.backward(dlogits.contiguous(), need_dx=ctx.needs_input_grad[0])
         grads = tuple(eng.g[k].clone() for k in eng.shapes)
-        return (None, None, None) + grads
+        return (dx, None, None) + grads
 
 
 class _Variable:
@@ -53,10 +54,11 @@ class _Variable:
 
 class Model(torch.nn.Module):
     def __init__(self, num_classes=60, in_channels=3, device="cuda", seed=0, stream="joint", mfma="fp32",
-                 trainable_adjacency=False):
+                 trainable_adjacency=False, blocks=None):
         """stream (not in the reference's constructor, which reads pre-computed files): 'joint', 'bone', 'joint_motion'
         or 'bone_motion' -- the bone (data_gen/gen_bone_data.py) and motion (data_gen/gen_motion_data.py) transforms are
         applied on the fly to JOINT input inside the data_bn prologue, bit-exactly.
+        blocks (not in the reference's constructor either): another stack of (filters, stride, residual) than the reference's ten.
         mfma: 'fp32' (the reference's arithmetic on the fp32 MFMA), 'f32_split' (fp32 storage and results, the contractions as three
         products of fp16 terms on the fp16 matrix pipe: same parity tolerances, 1.6x the training rate; 'f32_split_bf16x6': six
         products of bf16 terms) or 'bf16' (bf16 activations and MFMA operands, fp32 everything else: sar_amd/stgcn.py)."""
@@ -65,7 +67,7 @@ class Model(torch.nn.Module):
         from sar_amd.bone import NTU_BONE_PAIRS
         self.engine = STGCN(num_classes=num_classes, in_channels=in_channels, device=device, seed=seed,
                             bone_pairs=NTU_BONE_PAIRS if stream.startswith("bone") else None,
-                            motion=stream.endswith("motion"), mfma=mfma, trainable_adjacency=trainable_adjacency)
+                            motion=stream.endswith("motion"), mfma=mfma, trainable_adjacency=trainable_adjacency, blocks=blocks)
         # parameters are views into the engine's flat fp32 buffer (one all-reduce bucket, fused optimizer)
         self._names = list(self.engine.shapes)
         for k in self._names:

@@ -108,6 +108,8 @@ SIGNATURES = {
     "sar_data_bn_stats_f32": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp]),
     "sar_data_bn_apply_f32": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _i64, _fp]),
     "sar_data_bn_bwd_reduce_f32": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _i64, _fp, _fp, _fp]),
+    "sar_data_bn_bwd_apply_f32": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
+    "sar_data_bn_dx_frames": (_i, []),
     # block tail: optional pointers (mask, amax cells, tail) are None when unused (include/sar_hip.h)
     "sar_bn_add_relu_fwd_f32": (_i, [_fp, _fp, _fp, _i] + [_fp] * 6 + [_i, _i64, _i64, _fp]),
     "sar_bn_add_relu_bwd_reduce_f32": (_i, [_fp] * 8 + [_i, _i, _i64, _i64, C.POINTER(BnTail), _fp]),
@@ -223,6 +225,7 @@ SIGNATURES = {
     "sar_affine2_cn8": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i64, _i64, _fp]),
     "sar_data_bn_apply_cn8": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _i64, _fp]),
     "sar_data_bn_bwd_reduce_cn8": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _i64, _fp, _fp, _fp]),
+    "sar_data_bn_bwd_apply_cn8": (_i, [_fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
     "sar_pool_fwd_cn8": (_i, [_fp, _i64, _i, _i, _i, _i, _fp, _fp]),
     "sar_pool_bwd_cn8": (_i, [_fp, _i64, _i, _i, _i, _i, _fp, _fp]),
     "sar_cn_to_cn8": (_i, [_fp, _i64, _fp, _i64, _i, _i64, _fp]),

@@ -522,6 +522,31 @@ def data_bn_bwd_reduce(x, bone_parent, dy, mean, partials, motion=False):
                                               ptr(partials), stream_ptr()), "sar_data_bn_bwd_reduce_f32")
 
 
+DATA_BN_DX_FRAMES = 16    # frames of dx per workgroup of data_bn_bwd_apply (= sar_data_bn_dx_frames(); tests/test_data_bn_dx_abi.py)
+
+
+def _data_bn_dx_out(x, dx):
+    """the (N, C, T, V, M) float32 output of the backward apply pass"""
+    assert x.dim() == 5 and x.dtype == torch.float32 and x.is_cuda and x.is_contiguous(), "need a contiguous cuda float32 clip"
+    if dx is None:
+        dx = torch.empty_like(x)
+    assert dx.shape == x.shape and dx.dtype == torch.float32 and dx.is_cuda and dx.is_contiguous()
+    return dx
+
+
+def data_bn_bwd_apply(x, bone_parent, dy, k, dx=None, motion=False):
+    """d loss / d x (N, C, T, V, M) from dy = d loss / d data_bn(x) (CN rows [C][ld >= N*M*T*V]) and k = (k1, k2, k3) of
+    bn_bwd_finalize; include/sar_hip.h has the formulas"""
+    dx = _data_bn_dx_out(x, dx)
+    N, C_, T, V, M = x.shape
+    assert _f32(dy).dim() == 2 and dy.shape[0] == C_
+    ld = dy.stride(0) if C_ > 1 else dy.shape[1]        # (torch gives a single row whatever stride it likes: its width counts)
+    check(L.load().sar_data_bn_bwd_apply_f32(ptr(x), N, C_, T, V, M, ptr(bone_parent), int(motion), ptr(dy), ld,
+                                             ptr(_f32(k[0])), ptr(_f32(k[1])), ptr(_f32(k[2])), ptr(dx), stream_ptr()),
+          "sar_data_bn_bwd_apply_f32")
+    return dx
+
+
 RELU_MASK = os.environ.get("SAR_RELU_MASK", "1") == "1"   # block tails write / read a 1-bit ReLU mask (A/B switch)
 
 

@@ -210,6 +210,17 @@ def data_bn_bwd_reduce(x, bone_parent, dy, mean, partials, motion=False):
                                               ptr(mean), ptr(partials), stream_ptr()), "sar_data_bn_bwd_reduce_cn8")
 
 
+def data_bn_bwd_apply(x, bone_parent, dy, k, dx=None, motion=False):
+    """ops.data_bn_bwd_apply with dy = the (C <= 8)-channel CN8 plane; dx is float32 (N, C, T, V, M)"""
+    from .ops import _data_bn_dx_out
+    dx = _data_bn_dx_out(x, dx)
+    N, C_, T, V, M = x.shape
+    check(L.load().sar_data_bn_bwd_apply_cn8(ptr(x), N, C_, T, V, M, ptr(bone_parent), int(motion), ptr(_cn8(dy)), dy.shape[1],
+                                             ptr(_f32(k[0])), ptr(_f32(k[1])), ptr(_f32(k[2])), ptr(dx), stream_ptr()),
+          "sar_data_bn_bwd_apply_cn8")
+    return dx
+
+
 def pool_fwd(y, channels, B, TV, Mp, feat):
     check(L.load().sar_pool_fwd_cn8(ptr(_cn8(y)), y.shape[1], channels, B, TV, Mp, ptr(feat), stream_ptr()), "sar_pool_fwd_cn8")
 

@@ -134,6 +134,7 @@ class STGCN(FlatEngine):
         if bone_pairs is not None:
             bp = np.full(self.V, -1, dtype=np.int32)
             for v1, v2 in bone_pairs:          # data_gen/gen_bone_data.py:36-41 (1-based pairs)
+                assert 1 <= v1 <= self.V and 1 <= v2 <= self.V, "bone pair (%d, %d) outside 1..%d" % (v1, v2, self.V)
                 bp[v1 - 1] = v2 - 1
             self.bone_parent = torch.from_numpy(bp).to(dev)
 
@@ -589,12 +590,14 @@ class STGCN(FlatEngine):
         finally:
             self._flushing = False
 
-    def backward(self, dlogits, bucket_cb=None):
+    def backward(self, dlogits, bucket_cb=None, need_dx=False):
         """dlogits (N, classes) -> fills self.grad (every trainable parameter).  main_gnn.py:233.  bucket_cb: see
-        _bucket_done (the data-parallel exchange starts per bucket while backward is still running)."""
+        _bucket_done (the data-parallel exchange starts per bucket while backward is still running).  need_dx additionally returns
+        d loss / d x, float32 (N, C, T, V, M): the backward apply pass of data_bn, one more launch behind the last bucket (a
+        per-rank quantity, never exchanged); without it the launches are those of a step that asks for no input gradient."""
         if self.cn8:
             from . import stgcn8
-            return stgcn8.backward(self, dlogits, bucket_cb)
+            return stgcn8.backward(self, dlogits, bucket_cb, need_dx)
         sv = self._saved
         assert sv is not None, "backward() needs a preceding forward(training=True)"
         dev, V = dlogits.device, self.V
@@ -629,13 +632,17 @@ class STGCN(FlatEngine):
             self._buckets_after_block(i, bucket_cb)
         if self.dense_A:
             self._dense_backward_end()
-        # data_bn gamma/beta (the input needs no gradient)
+        # data_bn gamma/beta; the input's gradient only on request (need_dx)
         x = sv["x"]
         nch = V * self.C_in
         part = torch.empty((nch, N, 2), dtype=torch.float32, device=dev)
         ops.data_bn_bwd_reduce(x, self.bone_parent, dY, self.bn["data_bn"].mean, part, self.motion)
-        self._bn_backward("data_bn", (part, N), 2, 1, N * M * sv["T"], coefficients=False)
+        self._bn_backward("data_bn", (part, N), 2, 1, N * M * sv["T"], coefficients=need_dx)
         self._finish_backward(bucket_cb)
+        if need_dx:     # behind the last bucket's hand-over: the exchange does not wait for it
+            b = self.bn["data_bn"]
+            return ops.data_bn_bwd_apply(x, self.bone_parent, dY, (b.k1, b.k2, b.k3), motion=self.motion)
+        return None
 
     def _fuse_tail_f32(self):
         """SAR_EPI_ADD_GATE in the fp32 graph data gradient (SAR_F32_FUSE_TAIL=0 turns it off): plain ST-GCN engine, fp32 MFMA
@@ -819,16 +826,17 @@ class STGCN(FlatEngine):
         return dX
 
     # ------------------------------------------------------------------ training step
-    def loss_and_grad(self, x, labels, global_batch_size=None, bucket_cb=None):
-        """main_gnn.py:221-233: loss = sum CE / global_batch; gradients of every trainable variable.  bucket_cb: backward()."""
+    def loss_and_grad(self, x, labels, global_batch_size=None, bucket_cb=None, need_dx=False):
+        """main_gnn.py:221-233: loss = sum CE / global_batch; gradients of every trainable variable.  bucket_cb: backward().
+        need_dx: returns (logits, loss, d loss / d x) as ResNet18Engine.loss_and_grad does."""
         logits = self.forward(x, training=True)
         N = x.shape[0]
         gbs = global_batch_size or N
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dlogits = torch.empty_like(logits)
         ops.softmax_ce(logits, labels, 1.0 / gbs, loss, dlogits)
-        self.backward(dlogits, bucket_cb)
-        return logits, loss
+        dx = self.backward(dlogits, bucket_cb, need_dx)
+        return (logits, loss, dx) if need_dx else (logits, loss)
 
     def sgd_step(self, lr, momentum=0.9):
         """tf.keras SGD(momentum, nesterov=True) over the flat buffers (main_gnn.py:312-314)."""

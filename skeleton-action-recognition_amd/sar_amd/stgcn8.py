@@ -92,7 +92,7 @@ def _block_forward(eng, i, X, cin, f, s, B, T, training, saved, keep):
     return y, To
 
 
-def backward(eng, dlogits, bucket_cb=None):
+def backward(eng, dlogits, bucket_cb=None, need_dx=False):
     sv = eng._saved
     assert sv is not None, "backward() needs a preceding forward(training=True)"
     dev, V = dlogits.device, eng.V
@@ -113,13 +113,17 @@ def backward(eng, dlogits, bucket_cb=None):
         if eng._deferred:
             eng._flush_deferred()
         eng._buckets_after_block(i, bucket_cb)
-    # data_bn gamma / beta need the input gradient of block 0 (the input itself needs none)
+    # data_bn gamma / beta need the input gradient of block 0; the input's own gradient only on request (need_dx, STGCN.backward)
     x = sv["x"]
     nch = V * eng.C_in
     part = torch.empty((nch, N, 2), dtype=torch.float32, device=dev)
     ops8.data_bn_bwd_reduce(x, eng.bone_parent, dY, eng.bn["data_bn"].mean, part, eng.motion)
-    eng._bn_backward("data_bn", (part, N), 2, 1, N * M * sv["T"], coefficients=False)
+    eng._bn_backward("data_bn", (part, N), 2, 1, N * M * sv["T"], coefficients=need_dx)
     eng._finish_backward(bucket_cb)
+    if need_dx:
+        b = eng.bn["data_bn"]
+        return ops8.data_bn_bwd_apply(x, eng.bone_parent, dY, (b.k1, b.k2, b.k3), motion=eng.motion)
+    return None
 
 
 def _block_backward(eng, i, sb, dY, B, gated=None, below=None):
