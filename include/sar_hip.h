@@ -453,6 +453,17 @@ int sar_vr_signal_bwd_nparts(int B, int T);
 int sar_vr_signal_bwd_f32(const float* x, int B, int T, int V, int M, const int32_t* e_src, const int32_t* e_dst,
                           int E, const float* loc, const float* wavelength, const float* dz_re, const float* dz_im,
                           float* partials, sar_stream_t s);
+/* sar_vr_signal_bwd_x_f32: the gradient with respect to the SKELETON, dx (B,3,T,V,M) contiguous in the layout of x,
+ *   dx = d/dx sum_{b,t} (dz_re z_re + dz_im z_im) with z as sar_vr_signal_f32 computes it: the reverse mode of :93-123 with the
+ *   phase term, the amplitude term through the aspect angle of both joints of an edge, and the coupling of all edges of a body
+ *   through c = (mean_e |s_e - d_e|)^2.  Gather form with a fixed edge order, no atomics: bitwise reproducible, and a clip's
+ *   gradient does not depend on the rest of the batch.  Every element of dx is written; joints in no edge get 0.f.
+ *   Degenerate points (a joint at the radar position, a zero-length edge, |A| = 0, |u| = 1, an absent all-zero body) take the
+ *   zero subgradient, where the reference's autograd is NaN.  Limits (SAR_E_ARG otherwise): M <= 4, B <= 65535, the two
+ *   one-body LDS slabs 2 * 3 * 64 * (V | 1) floats + 2 E ints within 64 KB (V <= 41 at E = 24), B*3*T*V*M < 2^31. */
+int sar_vr_signal_bwd_x_f32(const float* x, int B, int T, int V, int M, const int32_t* e_src, const int32_t* e_dst,
+                            int E, const float* loc, const float* wavelength, const float* dz_re, const float* dz_im,
+                            float* dx, sar_stream_t s);
 
 /* Frame-rate up-sampling of utils.py:134-140 (Dataset.pad_frames, what main_spectrogram.py feeds the radar:
  * gaussian_filter1d(sigma) along T, then interp1d 'cubic' evaluated at np.linspace(0, 1, P*T), P = num_pad_frames = 250)

@@ -546,6 +546,165 @@ __global__ __launch_bounds__(FRAMES) void vr_signal_bwd_kernel(const float* __re
   }
 }
 
+// Signal stage, gradient with respect to the SKELETON (sar_vr_signal_bwd_x_f32): dx = d/dx sum_{b,t} (dz_re z_re + dz_im z_im),
+// the reverse mode of layers/virtual_radar.py:93-123.  The forward's frame-per-lane wave, one body at a time through two LDS slabs
+// (vr_signal_fast_kernel's scheme): xs holds the body's coordinates, gs the gradient rows of the same 64 frames.  A lane owns the
+// row of its frame: it walks the edges in their given order and adds each edge's two contributions into ITS row (no atomics, no
+// other lane touches the row), so the result is bitwise reproducible and a clip never sees the rest of the batch; the slab then
+// goes out with the lanes along the clip's memory order.  Joints that belong to no edge keep the 0.f the row was cleared to.
+//   per edge (s, d), e = s - loc, A = loc - (s + d)/2, B = d - s, u = <A,B> / (|A||B| + 1e-6) = cos(theta):
+//     den = (1 - u)(1 + u) + c u^2     (sin^2(theta) (cos^2(phi) + sin^2(phi)) + c cos^2(theta): phi cancels, so d den / d phi = 0)
+//     amp = sqrt(pi c) / |den|,  psi = 4 pi |e| / lambda,  P = dz_re cos(psi) + dz_im sin(psi),  Q = dz_im cos(psi) - dz_re sin(psi)
+//     phase:      d s += amp Q (4 pi / lambda) e / |e|
+//     amplitude:  g_den = -P amp / den,  g_u = g_den 2 u (c - 1),  d(s, d) += g_u du/d(s, d)
+//     coupling:   g_c  += P amp / (2 c) + g_den u^2      -- c = (mean_e |s_e - d_e|)^2 ties every edge of the body to every other,
+//   so a second walk over the edges distributes g_c: d(s, d) += +-g_c (2 sqrt(c) / E) (s - d) / |s - d|.
+// Range and phase keep the oracle's float32 operation order (IEEE sqrt and division), cos / sin of the phase share the float64
+// argument reduction of sincos_phase.  Degenerate points take the zero subgradient like vr_signal_bwd_kernel above: |e| = 0 (a
+// joint at the radar position), |A| = 0, |B| = 0 (a zero-length edge), |u| = 1, and an absent all-zero body (c = 0, amp = 0: all
+// of its rows are 0.f).  The reference's autograd is NaN at each of them -- for an absent body in EVERY coordinate of that body
+// (sqrt'(0) * 0 in the RCS), i.e. on most NTU clips.
+__global__ __launch_bounds__(FRAMES) void vr_signal_bwd_x_kernel(const float* __restrict__ x, int T, int V, int M,
+                                                                 const int* __restrict__ e_src, const int* __restrict__ e_dst,
+                                                                 int E, const float* __restrict__ loc_p,
+                                                                 const float* __restrict__ lam_p,
+                                                                 const float* __restrict__ dz_re,
+                                                                 const float* __restrict__ dz_im, float* __restrict__ dxo) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int VM = V * M;
+  const int RS = V | 1;                      // odd row stride
+  float* xs = smem;                          // [3][FRAMES][RS]: ONE body's coordinates
+  float* gs = xs + 3 * FRAMES * RS;          // [3][FRAMES][RS]: its gradient rows
+  int* es = (int*)(gs + 3 * FRAMES * RS);    // [E] src joints
+  int* ed = es + E;                          // [E] dst joints
+  const int b = blockIdx.y;
+  const int t0 = blockIdx.x * FRAMES;
+  const int nt = min(FRAMES, T - t0);
+  const int tt = threadIdx.x;
+  for (int i = tt; i < E; i += FRAMES) {
+    es[i] = e_src[i];
+    ed[i] = e_dst[i];
+  }
+  const float lx = loc_p[0], ly = loc_p[1], lz = loc_p[2];
+  const float lam = lam_p[0];
+  const float PI_F = 3.14159274101257324f;        // float32(np.pi)
+  const float FOURPI_F = 12.5663706143591725f;    // rounds to float32(4*np.pi)
+  float ur = 0.f, ui = 0.f;
+  if (tt < nt) {
+    ur = dz_re[(int64_t)b * T + t0 + tt];
+    ui = dz_im[(int64_t)b * T + t0 + tt];
+  }
+  for (int m = 0; m < M; ++m) {
+    __syncthreads();   // the previous body's slabs have been consumed (and es / ed are visible)
+    for (int c = 0; c < 3; ++c) {
+      const float* g = x + (((int64_t)b * 3 + c) * T + t0) * VM;   // nt*VM contiguous floats
+      for (int i = tt; i < nt * V; i += FRAMES) {
+        const int f = i / V, v = i - f * V;
+        xs[(c * FRAMES + f) * RS + v] = g[f * VM + v * M + m];
+        gs[(c * FRAMES + f) * RS + v] = 0.f;
+      }
+    }
+    __syncthreads();
+    if (tt < nt) {
+      const float* X0 = xs + (0 * FRAMES + tt) * RS;
+      const float* X1 = xs + (1 * FRAMES + tt) * RS;
+      const float* X2 = xs + (2 * FRAMES + tt) * RS;
+      float* G0 = gs + (0 * FRAMES + tt) * RS;
+      float* G1 = gs + (1 * FRAMES + tt) * RS;
+      float* G2 = gs + (2 * FRAMES + tt) * RS;
+      // c = (mean_e |S - D|)^2, layers/virtual_radar.py:110-113 (mean over the edge axis); amplitude only: 1-ulp square root
+      float acc = 0.f;
+      for (int e = 0; e < E; ++e) {
+        const int js = es[e], jd = ed[e];
+        const float dx = X0[js] - X0[jd], dy = X1[js] - X1[jd], dz = X2[js] - X2[jd];
+        acc = acc + __builtin_amdgcn_sqrtf((dx * dx + dy * dy) + dz * dz);
+      }
+      const float cbar = acc / (float)E;
+      const float c = cbar * cbar;
+      if (c > 0.f) {   // an absent body keeps its cleared rows
+        const float spc = sqrtf(PI_F * c);
+        const float kpsi = FOURPI_F / lam;
+        // Only u, the range and the phase need the oracle's roundings (IEEE sqrt and division).  Every quotient below them is a factor
+        // of the gradient alone: the 1-ulp reciprocal (v_rcp_f32 / v_rsq_f32) instead of the IEEE sequence, eight times per edge.
+        float gc_amp = 0.f, gc_den = 0.f;
+        for (int e = 0; e < E; ++e) {
+          const int js = es[e], jd = ed[e];
+          const float sx = X0[js], sy = X1[js], sz = X2[js];
+          const float dx = X0[jd], dy = X1[jd], dz = X2[jd];
+          // range and phase: the oracle's operation order, IEEE sqrt and division
+          const float ex = sx - lx, ey = sy - ly, ez = sz - lz;
+          const float rx = fabsf(ex), ry = fabsf(ey), rz = fabsf(ez);
+          const float rxy2 = rx * rx + ry * ry;
+          const float dist = sqrtf(rxy2 + rz * rz);
+          const float psi = ((FOURPI_F * dist) / (lam));
+          const float ax = lx - ((sx + dx) / (2.f)), ay = ly - ((sy + dy) / (2.f)), az = lz - ((sz + dz) / (2.f));
+          const float bx = dx - sx, by = dy - sy, bz = dz - sz;
+          const float dot = (ax * bx + ay * by) + az * bz;
+          const float nA = sqrtf((ax * ax + ay * ay) + az * az);
+          const float nB = sqrtf((bx * bx + by * by) + bz * bz);
+          const float den_u = nA * nB + 1e-6f;
+          const float u = dot / den_u;
+          const float su2 = (1.f - u) * (1.f + u);
+          const float den = fmaf(c * u, u, su2);
+          float sn, cs;
+          sincos_phase(psi, sn, cs);
+          const float iden = den != 0.f ? __builtin_amdgcn_rcpf(den) : 0.f;
+          const float amp = spc * fabsf(iden);
+          const float P = ur * cs + ui * sn, Q = ui * cs - ur * sn;
+          // phase term
+          const float gr = dist > 0.f ? ((amp * Q) * kpsi) * __builtin_amdgcn_rcpf(dist) : 0.f;
+          float gsx = gr * ex, gsy = gr * ey, gsz = gr * ez;
+          float gdx = 0.f, gdy = 0.f, gdz = 0.f;
+          // amplitude term through u = cos(theta)
+          const float gden = -(P * amp) * iden;
+          gc_amp += P * amp;                                       // d amp / d c at fixed den = amp / (2 c)
+          gc_den += gden * (u * u);                                // d den / d c = u^2
+          const float gu = su2 > 0.f ? gden * (2.f * u * (c - 1.f)) : 0.f;
+          // u = dot / (nA nB + 1e-6): d dot / ds = -B/2 - A, d dot / dd = -B/2 + A, d nA / d(s, d) = -A / (2 nA), d nB / d(s, d) = -+B / nB
+          const float k0 = gu * __builtin_amdgcn_rcpf(den_u);
+          const float ka = nA > 0.f ? (0.5f * u * nB) * __builtin_amdgcn_rcpf(nA) : 0.f;   // -u nB dnA
+          const float kb = nB > 0.f ? (u * nA) * __builtin_amdgcn_rcpf(nB) : 0.f;          // u nA B / nB: + for s, - for d
+          gsx += k0 * ((-0.5f * bx - ax) + ka * ax + kb * bx);
+          gsy += k0 * ((-0.5f * by - ay) + ka * ay + kb * by);
+          gsz += k0 * ((-0.5f * bz - az) + ka * az + kb * bz);
+          gdx += k0 * ((-0.5f * bx + ax) + ka * ax - kb * bx);
+          gdy += k0 * ((-0.5f * by + ay) + ka * ay - kb * by);
+          gdz += k0 * ((-0.5f * bz + az) + ka * az - kb * bz);
+          G0[js] += gsx;
+          G1[js] += gsy;
+          G2[js] += gsz;
+          G0[jd] += gdx;
+          G1[jd] += gdy;
+          G2[jd] += gdz;
+        }
+        // the coupling through c: d c / d s_e = (2 cbar / E) (s - d) / |s - d| = -(2 cbar / E) B / nB, d c / d d_e = the opposite
+        const float gc = gc_amp / (2.f * c) + gc_den;
+        const float kc = gc * (2.f * cbar / (float)E);
+        for (int e = 0; e < E; ++e) {
+          const int js = es[e], jd = ed[e];
+          const float bx = X0[jd] - X0[js], by = X1[jd] - X1[js], bz = X2[jd] - X2[js];
+          const float nB2 = (bx * bx + by * by) + bz * bz;
+          const float k = nB2 > 0.f ? kc * __builtin_amdgcn_rsqf(fmaxf(nB2, 1e-36f)) : 0.f;   // (the operand stays a normal number)
+          G0[js] -= k * bx;
+          G1[js] -= k * by;
+          G2[js] -= k * bz;
+          G0[jd] += k * bx;
+          G1[jd] += k * by;
+          G2[jd] += k * bz;
+        }
+      }
+    }
+    __syncthreads();
+    for (int c = 0; c < 3; ++c) {
+      float* g = dxo + (((int64_t)b * 3 + c) * T + t0) * VM;
+      for (int i = tt; i < nt * V; i += FRAMES) {
+        const int f = i / V, v = i - f * V;
+        g[f * VM + v * M + m] = gs[(c * FRAMES + f) * RS + v];
+      }
+    }
+  }
+}
+
 // Up-sampling preparation (utils.py:134-140, Dataset.pad_frames): per series (clip, coordinate, joint, body) along T
 //   1. scipy.ndimage.gaussian_filter1d(sigma, mode='reflect', truncate=4): symmetric FIR of radius int(4 sigma + .5),
 //      accumulated in float64 in scipy's order (centre, then the farthest pair inwards), stored as float32 (the
@@ -1041,6 +1200,25 @@ extern "C" int sar_vr_signal_bwd_f32(const float* x, int B, int T, int V, int M,
   hipLaunchKernelGGL(vr_signal_bwd_kernel<0>, grid, dim3(FRAMES), lds, as_stream(s), x, nullptr, T, T, V, M, e_src, e_dst,
                      E, loc, wavelength, dz_re, dz_im, partials);
   SAR_LAUNCH_CHECK("sar_vr_signal_bwd_f32");
+  return 0;
+}
+
+extern "C" int sar_vr_signal_bwd_x_f32(const float* x, int B, int T, int V, int M, const int32_t* e_src, const int32_t* e_dst,
+                                       int E, const float* loc, const float* wavelength, const float* dz_re,
+                                       const float* dz_im, float* dx, sar_stream_t s) {
+  SAR_REQUIRE(x && e_src && e_dst && loc && wavelength && dz_re && dz_im && dx, "sar_vr_signal_bwd_x_f32: null pointer");
+  SAR_REQUIRE(B > 0 && T > 0 && V > 0 && M > 0 && M <= 4 && E > 0, "sar_vr_signal_bwd_x_f32: bad sizes (M <= 4)");
+  // one body at a time: a coordinate slab and a gradient slab of V joints each, and the edge lists
+  const int64_t lds = (int64_t)sizeof(float) * 2 * 3 * FRAMES * ((int64_t)V | 1) + (int64_t)sizeof(int) * 2 * E;
+  SAR_REQUIRE(lds <= 64 * 1024, "sar_vr_signal_bwd_x_f32: V = %d (V*M = %lld) or E = %d too large for the LDS slabs", V,
+              (long long)V * M, E);
+  SAR_REQUIRE(B <= 65535, "sar_vr_signal_bwd_x_f32: B = %d beyond the grid's second dimension", B);
+  // (B <= 2^16, V*M <= 168 here: the product below cannot wrap)
+  SAR_REQUIRE((int64_t)B * 3 * T * V * M < (1ll << 31), "sar_vr_signal_bwd_x_f32: B*3*T*V*M must stay below 2^31");
+  dim3 grid((T + FRAMES - 1) / FRAMES, B);
+  hipLaunchKernelGGL(vr_signal_bwd_x_kernel, grid, dim3(FRAMES), (size_t)lds, as_stream(s), x, T, V, M, e_src, e_dst, E, loc,
+                     wavelength, dz_re, dz_im, dx);
+  SAR_LAUNCH_CHECK("sar_vr_signal_bwd_x_f32");
   return 0;
 }
 

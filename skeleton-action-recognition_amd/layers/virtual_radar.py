@@ -11,7 +11,22 @@ magnitude, roll).  The window is the one nnAudio 0.1.1's STFT builds
 (train_wavelength / train_radar_location, or `requires_grad = True` set later as main_spectrogram.py:133-136 does)
 the forward records an autograd node whose backward runs sar_stft_logmag_bwd_f32 (adjoint of the STFT / log-magnitude
 stage) and sar_vr_signal_bwd_f32 (forward-mode tangents of the geometry w.r.t. the 4 scalars, contracted with the
-signal cotangent).  The skeleton input gets no gradient (it is data).
+signal cotangent).
+
+The skeleton input gets a gradient too, as it does in the reference (whose layer is plain PyTorch): when `x.requires_grad`
+the same autograd node also runs sar_vr_signal_bwd_x_f32, the reverse mode of the signal stage (phase term, amplitude
+term through the aspect angle, the coupling of all edges of a body through the mean bone length), and returns
+d loss / d x in the layout of x -- whatever sits in front of the layer (models/lstm_sampler.py's TemporalSampler, an
+adversarial perturbation, a saliency map) gets its gradient, whether or not radar_location / wavelength / the Fourier
+kernels train.  `signal_backward_x(x, dz_re, dz_im)` is that stage on its own.  Two conventions:
+  * degenerate points take the ZERO subgradient (a joint at the radar position, a zero-length edge, |u| = 1, an absent
+    all-zero body: all of that body's coordinates get exactly 0).  The reference's autograd returns NaN there -- for an
+    absent body in every coordinate of that body, i.e. on most NTU clips;
+  * the on-GPU up-sampling (num_pad_frames > 0) is excluded: `x.requires_grad` with num_pad_frames > 0 raises
+    ValueError.  That path would differentiate through the Gaussian smoothing and the not-a-knot spline solve, and the
+    reference has no such gradient either (it up-samples in its numpy data loader).  Up-sampled data given directly is
+    an ordinary input.
+A forward whose x does not require a gradient issues exactly the launches it issued before.
 
 train_stft_kernel=True (layers/virtual_radar.py:71-76 -> nnAudio STFT(trainable=True)) turns the two conv1d Fourier kernels
 into the Parameters `stft.wcos` / `stft.wsin` of shape (n_fft, 1, n_fft) (window folded in, float32 of the float64
@@ -43,7 +58,7 @@ def gaussian_weights(sigma, truncate=4.0):
 
 
 class _RadarFunction(torch.autograd.Function):
-    """log|STFT(z(x; loc, lambda))| with gradients for radar_location and wavelength."""
+    """log|STFT(z(x; loc, lambda))| with gradients for radar_location, wavelength and the skeleton x."""
 
     @staticmethod
     def forward(ctx, loc, wavelength, mod, x, out_cols, num_pad_frames, sigma):
@@ -66,13 +81,18 @@ class _RadarFunction(torch.autograd.Function):
         dzr, dzi = torch.empty_like(zr), torch.empty_like(zi)
         check(lib.sar_stft_logmag_bwd_f32(ptr(zr), ptr(zi), B, T, mod.n_fft, mod.hop_length, ptr(mod.window), ctx.out_cols,
                                           ptr(dout), ptr(ws), ptr(dzr), ptr(dzi), stream_ptr()), "sar_stft_logmag_bwd_f32")
-        g = _signal_backward(mod, x, ctx.coef, ctx.P, dzr, dzi)
-        return g[:3].clone(), g[3].reshape(mod.wavelength.shape), None, None, None, None, None
+        dloc = dlam = dx = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g = _signal_backward(mod, x, ctx.coef, ctx.P, dzr, dzi)
+            dloc, dlam = g[:3].clone(), g[3].reshape(mod.wavelength.shape)
+        if ctx.needs_input_grad[3]:
+            dx = mod.signal_backward_x(x, dzr, dzi)
+        return dloc, dlam, None, dx, None, None, None
 
 
 class _KernelRadarFunction(torch.autograd.Function):
-    """The layer with nnAudio's trainable Fourier kernels: gradients for wcos / wsin and, when they train too, for
-    radar_location / wavelength."""
+    """The layer with nnAudio's trainable Fourier kernels: gradients for wcos / wsin and, when they want one too, for
+    radar_location / wavelength and the skeleton x."""
 
     @staticmethod
     def forward(ctx, loc, wavelength, wcos, wsin, mod, x, out_cols, num_pad_frames, sigma):
@@ -93,11 +113,12 @@ class _KernelRadarFunction(torch.autograd.Function):
         n_fft, hop = mod.n_fft, mod.hop_length
         dout = dout.contiguous().float()
         need_radar = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        need_x = ctx.needs_input_grad[5]
         nsplit = max(1, min(B * (T // hop + 1), 512 // max(1, n_fft // 16)))
         ws = torch.empty(lib.sar_stft_kernels_bwd_workspace_floats(B, T, n_fft, hop, nsplit), dtype=torch.float32, device=x.device)
         dw = torch.empty((2, n_fft, 1, n_fft), dtype=torch.float32, device=x.device)
-        dzr = torch.empty_like(zr) if need_radar else None
-        dzi = torch.empty_like(zi) if need_radar else None
+        dzr = torch.empty_like(zr) if need_radar or need_x else None
+        dzi = torch.empty_like(zi) if need_radar or need_x else None
         wcosT, wsinT = ctx.wT
         check(lib.sar_stft_kernels_bwd_f32(ptr(zr), ptr(zi), B, T, n_fft, hop, ptr(mod.stft.wcos.data), ptr(mod.stft.wsin.data),
                                            ptr(wcosT), ptr(wsinT), ctx.out_cols, ptr(dout), ptr(ws), nsplit, ptr(dw), ptr(dzr),
@@ -106,7 +127,8 @@ class _KernelRadarFunction(torch.autograd.Function):
         if need_radar:
             g = _signal_backward(mod, x, ctx.coef, ctx.P, dzr, dzi)
             dloc, dlam = g[:3].clone(), g[3].reshape(mod.wavelength.shape)
-        return dloc, dlam, dw[0], dw[1], None, None, None, None, None
+        dx = mod.signal_backward_x(x, dzr, dzi) if need_x else None
+        return dloc, dlam, dw[0], dw[1], None, dx, None, None, None
 
 
 def _signal_backward(mod, x, coef, P, dzr, dzi):
@@ -214,13 +236,34 @@ class VirtualRadar(torch.nn.Module):
                                              ptr(zi), stream_ptr()), "sar_vr_signal_f32")
         return zr, zi
 
+    def signal_backward_x(self, x, dz_re, dz_im):
+        """d/dx sum_{b,t} (dz_re z_re + dz_im z_im) for the signal (z_re, z_im) = self.signal(x): the gradient of the signal
+        stage with respect to the skeleton, (B,3,T,V,M) float32 in the layout of x (sar_vr_signal_bwd_x_f32).  dz_re / dz_im
+        (B,T): the signal cotangent, e.g. what sar_stft_logmag_bwd_f32 returns.  Zero subgradient at degenerate points."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[1] == 3
+        x = x.contiguous()
+        B, _, T, V, M = x.shape
+        assert max(max(self.src), max(self.dst)) < V and min(min(self.src), min(self.dst)) >= 0, "edge joint outside 0..V-1"
+        dz_re, dz_im = dz_re.contiguous(), dz_im.contiguous()
+        assert dz_re.shape == dz_im.shape == (B, T) and dz_re.dtype == dz_im.dtype == torch.float32
+        assert dz_re.device == dz_im.device == x.device
+        dx = torch.empty_like(x)
+        check(L.load().sar_vr_signal_bwd_x_f32(ptr(x), B, T, V, M, ptr(self._src), ptr(self._dst), len(self.src),
+                                               ptr(self.radar_location.data), ptr(self.wavelength.data.reshape(1)), ptr(dz_re),
+                                               ptr(dz_im), ptr(dx), stream_ptr()), "sar_vr_signal_bwd_x_f32")
+        return dx
+
     def forward(self, x, out_cols=0, num_pad_frames=0, sigma=3):
         """out_cols > 0 produces only the frames a nearest-neighbour F.interpolate(..., out_cols) would read
         (models/resnet.py:26 fused as a column select) -> (B, n_fft, out_cols).
         num_pad_frames = P > 0: x is the RAW (B,3,T,V,M) clip and the result is what the reference computes from
         utils.Dataset.pad_frames(x) (Gaussian smoothing sigma + cubic interpolation to P*T frames, utils.py:134-140) --
-        the up-sampled tensor is never built."""
-        radar_grad = self.radar_location.requires_grad or self.wavelength.requires_grad
+        the up-sampled tensor is never built.
+        x.requires_grad: the result carries d / dx (module docstring); not with num_pad_frames > 0 (ValueError)."""
+        if torch.is_grad_enabled() and x.requires_grad and num_pad_frames:
+            raise ValueError("VirtualRadar: no gradient with respect to x through the on-GPU up-sampling (num_pad_frames = %d): "
+                             "detach x, or up-sample in front of the layer and pass num_pad_frames = 0" % num_pad_frames)
+        radar_grad = self.radar_location.requires_grad or self.wavelength.requires_grad or x.requires_grad
         if self.stft is not None:      # nnAudio's trainable kernels: always the matrix product with their current values
             if torch.is_grad_enabled() and (radar_grad or self.stft.wcos.requires_grad or self.stft.wsin.requires_grad):
                 return _KernelRadarFunction.apply(self.radar_location, self.wavelength, self.stft.wcos, self.stft.wsin, self,
