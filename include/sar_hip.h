@@ -294,6 +294,15 @@ int sar_bn_finalize_f32(const float* partials, int nparts, int C, double count, 
                         int unbiased_running, const float* gamma, const float* beta,
                         float* running_mean, float* running_var,
                         float* mean, float* rstd, float* scale, float* shift, sar_stream_t s);
+/* The same from partials of (x - pivot[c]): [C][nparts][2] = (sum (x-p), sum (x-p)^2) with p = pivot[c], a float32 value near the
+ * channel's mean (the second pass of a two-pass reduction: sar_data_bn_stats_pivot_f32).
+ *   mean = p + S1/count ; var = S2/count - (S1/count)^2
+ * so the cancellation costs 2^-24 (mean - p)^2 / var of the variance instead of 2^-24 mean^2 / var.  pivot == NULL: p = 0,
+ * sar_bn_finalize_f32 exactly. */
+int sar_bn_finalize_pivot_f32(const float* partials, int nparts, int C, double count, const float* pivot, float eps, float momentum,
+                              int unbiased_running, const float* gamma, const float* beta,
+                              float* running_mean, float* running_var,
+                              float* mean, float* rstd, float* scale, float* shift, sar_stream_t s);
 /* inference affine from the moving statistics (training=False path, main_gnn.py:207). */
 int sar_bn_eval_affine_f32(const float* gamma, const float* beta, const float* running_mean,
                            const float* running_var, float eps, int C, float* scale, float* shift, sar_stream_t s);
@@ -312,6 +321,15 @@ int sar_bn_bwd_finalize_f32(const float* partials, int nparts, int64_t chan_stri
  * the motion stream (data_gen/gen_motion_data.py:24-27): frame t+1 minus frame t of the joint / bone data, last frame 0. */
 int sar_data_bn_stats_f32(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent, int motion,
                           float* partials /* [V*C][N][2] */, sar_stream_t s);
+/* Two-pass statistics for un-centred coordinates (data_bn sees the raw clip: a depth channel sits many standard deviations from 0).
+ * Pass 1 is sar_data_bn_stats_f32.  From its sums, per channel ch of the V*C: pivot[ch] = float32(mean) where
+ * mean^2 > 4 var (the channel lies more than 2 standard deviations from 0, or its one-pass variance came out <= 0 beside a mean
+ * that is not 0), else 0.  Pass 2 replaces the partials of the channels with pivot != 0 by those of (x - pivot[ch]); a channel
+ * with pivot 0 keeps its first-pass sums, which lose at most 2^-22 of its variance, bit for bit what sar_data_bn_stats_f32
+ * leaves.  For sar_bn_finalize_pivot_f32.  Three launches on stream s; x is read twice only where a channel has a pivot.  An
+ * all-zero channel has pivot, sums, mean and var exactly 0. */
+int sar_data_bn_stats_pivot_f32(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent, int motion,
+                                float* pivot /* [V*C] */, float* partials /* [V*C][N][2] */, sar_stream_t s);
 int sar_data_bn_apply_f32(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent, int motion,
                           const float* scale, const float* shift, float* out, int64_t ld_out, sar_stream_t s);
 /* backward: partials [V*C][N][2] = (sum dy, sum dy*(x_raw - mean[ch])) from dy in CN layout (mean may be NULL). */

@@ -120,7 +120,8 @@ __global__ __launch_bounds__(TPB) void bn_finalize_kernel(const float* __restric
                                                           float eps, float momentum, int unbiased_running,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           float* running_mean, float* running_var, float* mean_o,
-                                                          float* rstd_o, float* scale_o, float* shift_o) {
+                                                          float* rstd_o, float* scale_o, float* shift_o,
+                                                          const float* __restrict__ pivot) {
   const int c = blockIdx.x;
   // (sum, sum of squares) pairs: 8-byte loads, four independent fp64 chains per thread so that the loads overlap
   const float2* p = reinterpret_cast<const float2*>(partials) + (int64_t)c * nparts;
@@ -153,8 +154,9 @@ __global__ __launch_bounds__(TPB) void bn_finalize_kernel(const float* __restric
   if (threadIdx.x == 0) {
     s1 = red[0][0] + red[0][1] + red[0][2] + red[0][3];
     s2 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
+    // partials of (x - pivot): the mean moves back by the pivot, the variance does not notice it
+    const double m1 = s1 / count, mean = pivot ? (double)pivot[c] + m1 : m1;
+    double var = s2 / count - m1 * m1;
     if (var < 0.0) var = 0.0;
     const double rstd = 1.0 / sqrt(var + (double)eps);
     const double g = gamma ? (double)gamma[c] : 1.0, b = beta ? (double)beta[c] : 0.0;
@@ -168,6 +170,25 @@ __global__ __launch_bounds__(TPB) void bn_finalize_kernel(const float* __restric
       running_var[c] = (float)((double)momentum * running_var[c] + (1.0 - (double)momentum) * vr);
     }
   }
+}
+
+// The pivot of a two-pass reduction from the partials [C][nparts][2] of its first pass (the sums in fp64, i ascending): the float32
+// mean where the channel needs one, 0 where it does not.  var = S2/n - mean^2 loses 2^-24 (mean/std)^2 of the variance, so a
+// channel within SAR_PIVOT_RATIO = 2 standard deviations of 0 (by the first pass's own statistics) loses at most 2^-22: its
+// first-pass sums ARE its statistics, pivot 0, and the second pass leaves them as they are.  A first-pass variance that came out
+// negative or 0 beside a mean that is not 0 is a channel that needs the pivot.
+constexpr double SAR_PIVOT_RATIO = 2.0;   // = PIVOT_RATIO of tests/bn_stats_reference.py (tests/test_bn_stats_reference.py reads this line)
+__global__ void bn_pivot_kernel(const float* __restrict__ partials, int nparts, int C, double count, float* __restrict__ pivot) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float2* p = reinterpret_cast<const float2*>(partials) + (int64_t)c * nparts;
+  double a = 0.0, b = 0.0;
+  for (int i = 0; i < nparts; ++i) {
+    a += (double)p[i].x;
+    b += (double)p[i].y;
+  }
+  const double m = a / count, var = b / count - m * m;
+  pivot[c] = (m * m > SAR_PIVOT_RATIO * SAR_PIVOT_RATIO * var) ? (float)m : 0.f;
 }
 
 __global__ void bn_eval_affine_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
@@ -250,7 +271,9 @@ __device__ __forceinline__ float load_joint(const float* slab, int t, int v, int
   return load_frame(slab, t + 1, v, m, V, M, bone_parent) - load_frame(slab, t, v, m, V, M, bone_parent);
 }
 
-template <bool BWD, bool DY_CN8 = false>
+// SECOND: the second pass of the forward statistics -- a channel whose pivot is 0 keeps the sums the first pass left in `partials`
+// (they are its sums of x - 0), so its threads read nothing and write nothing.
+template <bool BWD, bool DY_CN8 = false, bool SECOND = false>
 __global__ __launch_bounds__(TPB) void data_bn_reduce_kernel(const float* __restrict__ x, int N, int C, int T, int V, int M,
                                                              const int* __restrict__ bone_parent, int motion,
                                                              const float* __restrict__ dy, int64_t ld_dy,
@@ -263,8 +286,8 @@ __global__ __launch_bounds__(TPB) void data_bn_reduce_kernel(const float* __rest
   const int col = threadIdx.x % VM, rg = threadIdx.x / VM;
   const int v = col / M, m = col - v * M;
   float s1 = 0.f, s2 = 0.f;
-  const float mu = (BWD && mean && rg < groups) ? mean[v * C + c] : 0.f;
-  if (rg < groups) {
+  const float mu = (mean && rg < groups) ? mean[v * C + c] : 0.f;   // forward: the pivot of the second pass
+  if (rg < groups && !(SECOND && mu == 0.f)) {
     for (int t = rg; t < T; t += groups) {
       const float val = load_joint(slab, t, v, m, V, M, bone_parent, motion, T) - mu;
       if (BWD) {
@@ -287,7 +310,7 @@ __global__ __launch_bounds__(TPB) void data_bn_reduce_kernel(const float* __rest
   r1[threadIdx.x] = s1;
   r2[threadIdx.x] = s2;
   __syncthreads();
-  if (threadIdx.x < V) {
+  if (threadIdx.x < V && !(SECOND && mean[threadIdx.x * C + c] == 0.f)) {
     float a = 0.f, b = 0.f;
     for (int g = 0; g < groups; ++g)
       for (int mm = 0; mm < M; ++mm) {
@@ -819,16 +842,32 @@ extern "C" int sar_permute3_batch_f32(const float* in, float* out, const sar_per
   return 0;
 }
 
+// both finalisations: `fn` names the entry point in the error text, pivot == nullptr is the plain one
+static int bn_finalize(const char* fn, const float* partials, int nparts, int C, double count, const float* pivot, float eps,
+                       float momentum, int unbiased_running, const float* gamma, const float* beta, float* running_mean,
+                       float* running_var, float* mean, float* rstd, float* scale, float* shift, sar_stream_t s) {
+  SAR_REQUIRE(partials && nparts > 0 && C > 0 && count > 0 && scale && shift, "%s: bad arguments", fn);
+  SAR_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "%s: running stats mismatch", fn);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(TPB), 0, as_stream(s), partials, nparts, count, eps, momentum,
+                     unbiased_running, gamma, beta, running_mean, running_var, mean, rstd, scale, shift, pivot);
+  SAR_LAUNCH_CHECK(fn);
+  return 0;
+}
+
 extern "C" int sar_bn_finalize_f32(const float* partials, int nparts, int C, double count, float eps, float momentum,
                                    int unbiased_running, const float* gamma, const float* beta, float* running_mean,
                                    float* running_var, float* mean, float* rstd, float* scale, float* shift,
                                    sar_stream_t s) {
-  SAR_REQUIRE(partials && nparts > 0 && C > 0 && count > 0 && scale && shift, "sar_bn_finalize: bad arguments");
-  SAR_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "sar_bn_finalize: running stats mismatch");
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(TPB), 0, as_stream(s), partials, nparts, count, eps, momentum,
-                     unbiased_running, gamma, beta, running_mean, running_var, mean, rstd, scale, shift);
-  SAR_LAUNCH_CHECK("sar_bn_finalize_f32");
-  return 0;
+  return bn_finalize("sar_bn_finalize_f32", partials, nparts, C, count, nullptr, eps, momentum, unbiased_running, gamma, beta,
+                     running_mean, running_var, mean, rstd, scale, shift, s);
+}
+
+extern "C" int sar_bn_finalize_pivot_f32(const float* partials, int nparts, int C, double count, const float* pivot, float eps,
+                                         float momentum, int unbiased_running, const float* gamma, const float* beta,
+                                         float* running_mean, float* running_var, float* mean, float* rstd, float* scale,
+                                         float* shift, sar_stream_t s) {
+  return bn_finalize("sar_bn_finalize_pivot_f32", partials, nparts, C, count, pivot, eps, momentum, unbiased_running, gamma, beta,
+                     running_mean, running_var, mean, rstd, scale, shift, s);
 }
 
 extern "C" int sar_bn_eval_affine_f32(const float* gamma, const float* beta, const float* running_mean,
@@ -867,6 +906,23 @@ extern "C" int sar_data_bn_stats_f32(const float* x, int N, int C, int T, int V,
   hipLaunchKernelGGL(data_bn_reduce_kernel<false>, dim3(N * C), dim3(TPB), 0, as_stream(s), x, N, C, T, V, M,
                      bone_parent, motion, (const float*)nullptr, (int64_t)0, (const float*)nullptr, partials);
   SAR_LAUNCH_CHECK("sar_data_bn_stats_f32");
+  return 0;
+}
+
+extern "C" int sar_data_bn_stats_pivot_f32(const float* x, int N, int C, int T, int V, int M, const int32_t* bone_parent,
+                                           int motion, float* pivot, float* partials, sar_stream_t s) {
+  int rc = data_bn_check(x, N, C, T, V, M);
+  if (rc) return rc;
+  SAR_REQUIRE(pivot && partials, "sar_data_bn_stats_pivot: null pivot or partials");
+  // pass 1: the sums of x and x^2 -> the pivot (the float32 mean, or 0 for a channel near 0: bn_pivot_kernel); pass 2: the sums of
+  // (x - pivot) and (x - pivot)^2 over the same partials, for the channels whose pivot is not 0
+  hipLaunchKernelGGL(data_bn_reduce_kernel<false>, dim3(N * C), dim3(TPB), 0, as_stream(s), x, N, C, T, V, M,
+                     bone_parent, motion, (const float*)nullptr, (int64_t)0, (const float*)nullptr, partials);
+  hipLaunchKernelGGL(bn_pivot_kernel, dim3((V * C + 255) / 256), dim3(256), 0, as_stream(s), (const float*)partials, N, V * C,
+                     (double)N * M * T, pivot);
+  hipLaunchKernelGGL((data_bn_reduce_kernel<false, false, true>), dim3(N * C), dim3(TPB), 0, as_stream(s), x, N, C, T, V, M,
+                     bone_parent, motion, (const float*)nullptr, (int64_t)0, (const float*)pivot, partials);
+  SAR_LAUNCH_CHECK("sar_data_bn_stats_pivot_f32");
   return 0;
 }
 

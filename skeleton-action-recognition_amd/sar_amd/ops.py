@@ -484,7 +484,14 @@ def conv_wgrad(mode, src, dout, dW_out, *, B, V, T_src, T_out, Kc, M, taps, stri
 
 
 def bn_finalize(partials, nparts, C_, count, eps, momentum, unbiased_running, gamma, beta, running_mean, running_var,
-                mean, rstd, scale, shift):
+                mean, rstd, scale, shift, pivot=None):
+    """pivot: the per-channel float32 value the producer subtracted before it summed (data_bn_stats), or None"""
+    if pivot is not None:
+        check(L.load().sar_bn_finalize_pivot_f32(ptr(partials), nparts, C_, float(count), ptr(pivot), eps, momentum,
+                                                 int(unbiased_running), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
+                                                 ptr(mean), ptr(rstd), ptr(scale), ptr(shift), stream_ptr()),
+              "sar_bn_finalize_pivot_f32")
+        return
     check(L.load().sar_bn_finalize_f32(ptr(partials), nparts, C_, float(count), eps, momentum, int(unbiased_running),
                                        ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), ptr(mean), ptr(rstd),
                                        ptr(scale), ptr(shift), stream_ptr()), "sar_bn_finalize_f32")
@@ -504,8 +511,17 @@ def bn_bwd_finalize(partials, nparts, chan_stride, part_stride, off1, off2, C_, 
                                            ptr(k3), stream_ptr()), "sar_bn_bwd_finalize_f32")
 
 
-def data_bn_stats(x, bone_parent, partials, motion=False):
+def data_bn_stats(x, bone_parent, partials, motion=False, pivot=None):
+    """partials [V*C][N][2] of the clip's BatchNorm channels.  pivot (float32 [V*C], written here): two passes, the second sums
+    (x - pivot) with pivot = the first pass's mean for every channel more than 2 standard deviations from 0 (the others keep
+    pivot 0 and their first-pass sums, bit for bit), for bn_finalize(.., pivot=pivot) -- what the engines run, since raw
+    coordinates are not centred ("BatchNorm statistics on un-centred data").  pivot None: one pass, the sums of x, x^2."""
     N, C_, T, V, M = x.shape
+    if pivot is not None:
+        assert pivot.numel() == V * C_ and pivot.dtype == torch.float32 and pivot.is_contiguous()
+        check(L.load().sar_data_bn_stats_pivot_f32(ptr(x), N, C_, T, V, M, ptr(bone_parent), int(motion), ptr(pivot), ptr(partials),
+                                                   stream_ptr()), "sar_data_bn_stats_pivot_f32")
+        return
     check(L.load().sar_data_bn_stats_f32(ptr(x), N, C_, T, V, M, ptr(bone_parent), int(motion), ptr(partials), stream_ptr()),
           "sar_data_bn_stats_f32")
 

@@ -65,8 +65,9 @@ def ntu_adjacency():
 class _BN:
     """Per-BatchNorm device state: parameters are views of the flat buffer, statistics are buffers."""
 
-    def __init__(self, C, device):
+    def __init__(self, C, device, pivoted=False):
         z = lambda: torch.zeros(C, dtype=torch.float32, device=device)
+        self.pivot = z() if pivoted else None       # data_bn: the value its two-pass statistics subtract (ops.data_bn_stats)
         self.moving_mean, self.moving_var = z(), torch.ones(C, dtype=torch.float32, device=device)
         self.mean, self.rstd, self.scale, self.shift = z(), z(), z(), z()
         self.k1, self.k2, self.k3 = z(), z(), z()
@@ -183,7 +184,7 @@ class STGCN(FlatEngine):
         return total
 
     def _init_bn(self):
-        self.bn = {"data_bn": _BN(self.V * self.C_in, self.device)}
+        self.bn = {"data_bn": _BN(self.V * self.C_in, self.device, pivoted=True)}
         for i, (f, s, res) in enumerate(self.blocks):
             self._init_block_bn("l%d." % i, f, self.kinds[i])
 
@@ -372,7 +373,7 @@ class STGCN(FlatEngine):
         b = self.bn[name]
         if training:
             ops.bn_finalize(result[0], result[1], b.mean.numel(), count, BN_EPS, BN_MOMENTUM, unbiased, self.p[name + ".gamma"],
-                            self.p[name + ".beta"], b.moving_mean, b.moving_var, b.mean, b.rstd, b.scale, b.shift)
+                            self.p[name + ".beta"], b.moving_mean, b.moving_var, b.mean, b.rstd, b.scale, b.shift, pivot=b.pivot)
         else:
             self._bn_eval(name)
         return b
@@ -418,7 +419,7 @@ class STGCN(FlatEngine):
         part = None
         if training:
             part = torch.empty((V * Cin, N, 2), dtype=torch.float32, device=dev)
-            ops.data_bn_stats(x, self.bone_parent, part, self.motion)
+            ops.data_bn_stats(x, self.bone_parent, part, self.motion, pivot=self.bn["data_bn"].pivot)
         dbn = self._bn_forward("data_bn", (part, N), N * M * T, training, unbiased=False)
         h = torch.empty((Cin, B * T * V), dtype=torch.float32, device=dev)
         ops.data_bn_apply(x, self.bone_parent, dbn.scale, dbn.shift, h, self.motion)

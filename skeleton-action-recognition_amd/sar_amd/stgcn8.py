@@ -37,7 +37,7 @@ def forward(eng, x, training=True, keep=None):
     part = None
     if training:
         part = torch.empty((V * Cin, N, 2), dtype=torch.float32, device=dev)
-        ops.data_bn_stats(x, eng.bone_parent, part, eng.motion)
+        ops.data_bn_stats(x, eng.bone_parent, part, eng.motion, pivot=eng.bn["data_bn"].pivot)
     dbn = eng._bn_forward("data_bn", (part, N), N * M * T, training, unbiased=False)
     h = ops8.empty(Cin, B * T * V, dev)
     ops8.data_bn_apply(x, eng.bone_parent, dbn.scale, dbn.shift, h, eng.motion)
