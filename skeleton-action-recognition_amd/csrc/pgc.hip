@@ -284,10 +284,12 @@ __global__ __launch_bounds__(SMALL) void pgc_small_bwd_kernel(const float* __res
     ds_out[e] = dzp / sq;                                                          // dS
     pool[e] = -dzp / s;                                                            // d centers, pooled path
     pool[CJ + e] = -dzp * sv[O_ZP + e] / s;                                        // d s, pooled path
-    tmp[e] = -dzp * sv[O_S + e] / (sq * qs[j]);
+    // two quotients, not dzp S / (s qs^2): for a vertex that takes almost no column (qs below 1e-19) s qs^2 is denormal or 0 in
+    // float32 while dzp / (s qs) and S / qs -- a weighted mean of x -- are ordinary numbers
+    tmp[e] = (-dzp / sq) * (sv[O_S + e] / qs[j]);
   }
   __syncthreads();
-  if (t < PJ) {                                   // dqs[j] = -sum_c dzp S / (s qs^2)
+  if (t < PJ) {                                   // dqs[j] = -sum_c (dzp / (s qs)) (S / qs)
     float v = 0.f;
     for (int c = 0; c < PC; ++c) v += tmp[c * PJ + t];
     ds_out[CJ + t] = v;

@@ -999,15 +999,24 @@ PGC_FWD_PART, PGC_DH_PART, PGC_BWD_PART, PGC_SAVED, PGC_DSAVED, PGC_SLAB = 2080,
 
 
 def _pgc_args(x, B, P):
-    assert x.dtype == torch.float32 and x.is_cuda and x.shape[0] == PGC_C and x.stride(1) == 1 and x.shape[1] == B * P
+    """the row stride of a CN operand [64][B*P]; ValueError before the library is touched for sizes below 1, an operand that is no
+    float32 CUDA tensor, and one that is not 2-D with 64 rows, B * P columns of unit stride and a row stride >= B * P"""
+    if B < 1 or P < 1:
+        raise ValueError("ProjectionGraphConv needs B >= 1 and P >= 1 (got B = %d, P = %d)" % (B, P))
+    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.is_cuda):
+        raise ValueError("operands must be float32 CUDA tensors (got %s)" % (("%s on %s" % (x.dtype, x.device)) if torch.is_tensor(x)
+                                                                             else type(x).__name__))
+    if not (x.dim() == 2 and x.shape[0] == PGC_C and x.shape[1] == B * P and x.stride(1) == 1 and x.stride(0) >= B * P):
+        raise ValueError("a CN operand must be a 2-D tensor of %d rows and B * P = %d columns, contiguous or a row-strided view with a "
+                         "unit column stride (got shape %s, strides %s)" % (PGC_C, B * P, tuple(x.shape), tuple(x.stride())))
     return x.stride(0)
 
 
 def pgc_forward(x, B, P, centers, variance, W, bias, out):
     """out = x + the projection graph convolution of x (models/stpgcn.py:23-47).  Returns (q [32][B*P], saved [B][PGC_SAVED]):
     what the backward pass needs (saved: S | zp | zn | g | h | A | qs | sum_j zp^2 per sample)."""
+    ld, ld_out = _pgc_args(x, B, P), _pgc_args(out, B, P)
     lib, dev = L.load(), x.device
-    ld = _pgc_args(x, B, P)
     G = lib.sar_pgc_nparts(P)
     q = torch.empty((PGC_J, B * P), dtype=torch.float32, device=dev)
     part = torch.empty((B, G, PGC_FWD_PART), dtype=torch.float32, device=dev)
@@ -1016,7 +1025,7 @@ def pgc_forward(x, B, P, centers, variance, W, bias, out):
           "sar_pgc_assign_f32")
     check(lib.sar_pgc_small_fwd_f32(ptr(part), B, G, ptr(centers), ptr(variance), ptr(_f32(W)), ptr(_f32(bias)), ptr(saved),
                                     stream_ptr()), "sar_pgc_small_fwd_f32")
-    check(lib.sar_pgc_project_f32(ptr(x), ld, ptr(q), ptr(saved), B, P, ptr(out), _pgc_args(out, B, P), stream_ptr()),
+    check(lib.sar_pgc_project_f32(ptr(x), ld, ptr(q), ptr(saved), B, P, ptr(out), ld_out, stream_ptr()),
           "sar_pgc_project_f32")
     return q, saved
 
@@ -1024,19 +1033,21 @@ def pgc_forward(x, B, P, centers, variance, W, bias, out):
 def pgc_backward(x, dout, q, saved, B, P, centers, variance, W, dx, g_centers, g_variance, g_kernel_bias):
     """dx = the gradient w.r.t. x; g_centers / g_variance ([64][32]) and g_kernel_bias (the Conv1D kernel [64*64] followed by its
     bias [64], one contiguous range) are written, not accumulated.  Every sum runs in a fixed order."""
+    ld, ld_dout, ld_dx = _pgc_args(x, B, P), _pgc_args(dout, B, P), _pgc_args(dx, B, P)
+    if not (g_kernel_bias.is_contiguous() and g_kernel_bias.numel() == PGC_C * PGC_C + PGC_C):
+        raise ValueError("g_kernel_bias must be one contiguous range of %d elements (got shape %s, strides %s)"
+                         % (PGC_C * PGC_C + PGC_C, tuple(g_kernel_bias.shape), tuple(g_kernel_bias.stride())))
     lib, dev = L.load(), x.device
-    ld = _pgc_args(x, B, P)
     G = lib.sar_pgc_nparts(P)
-    assert g_kernel_bias.is_contiguous() and g_kernel_bias.numel() == PGC_C * PGC_C + PGC_C
     part = torch.empty((B, G, PGC_DH_PART), dtype=torch.float32, device=dev)
-    check(lib.sar_pgc_bwd_reduce_f32(ptr(dout), _pgc_args(dout, B, P), ptr(q), B, P, ptr(part), stream_ptr()), "sar_pgc_bwd_reduce_f32")
+    check(lib.sar_pgc_bwd_reduce_f32(ptr(dout), ld_dout, ptr(q), B, P, ptr(part), stream_ptr()), "sar_pgc_bwd_reduce_f32")
     dsaved = torch.empty((B, PGC_DSAVED), dtype=torch.float32, device=dev)
     slab = torch.empty((B, PGC_SLAB), dtype=torch.float32, device=dev)
     check(lib.sar_pgc_small_bwd_f32(ptr(part), B, G, ptr(_f32(variance)), ptr(_f32(W)), ptr(saved), ptr(dsaved), ptr(slab), stream_ptr()),
           "sar_pgc_small_bwd_f32")
     cpart = torch.empty((B, G, PGC_BWD_PART), dtype=torch.float32, device=dev)
-    check(lib.sar_pgc_bwd_column_f32(ptr(x), ld, ptr(dout), dout.stride(0), ptr(q), ptr(saved), ptr(dsaved), ptr(_f32(centers)),
-                                     ptr(variance), B, P, ptr(dx), _pgc_args(dx, B, P), ptr(cpart), stream_ptr()), "sar_pgc_bwd_column_f32")
+    check(lib.sar_pgc_bwd_column_f32(ptr(x), ld, ptr(dout), ld_dout, ptr(q), ptr(saved), ptr(dsaved), ptr(_f32(centers)),
+                                     ptr(variance), B, P, ptr(dx), ld_dx, ptr(cpart), stream_ptr()), "sar_pgc_bwd_column_f32")
     nwb = PGC_C * PGC_C + PGC_C
     sums = torch.empty(2 * PGC_BWD_PART, dtype=torch.float32, device=dev)      # column partials | pooled slabs
     check(lib.sar_slab_reduce_f32(ptr(slab), B, PGC_SLAB, nwb, ptr(g_kernel_bias), stream_ptr()), "sar_slab_reduce_f32")
