@@ -19,6 +19,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .engine import FlatEngine
+from .split_plan import OFF, BlockPlan, SplitPlan
 
 BN_EPS = 1e-3        # Keras BatchNormalization defaults (models/stgcn.py:27,37,56,111)
 BN_MOMENTUM = 0.99
@@ -44,6 +45,7 @@ AUX_STREAM = os.environ.get("SAR_STGCN_AUX_STREAM", "1") == "1"
 _COMPACT_SKIP = os.environ.get("SAR_COMPACT_SKIP", "fp32")
 # A/B switch: which kernel families of a split engine take the split kernels (default all that are built)
 _SPLIT_KINDS = set(os.environ.get("SAR_SPLIT_KINDS", "tfwd,tdgrad,twgrad,gfwd,gdgrad,gwgrad,rfwd,rdgrad,rwgrad").split(","))
+_NO_SPLIT = dict(split=None)      # the arithmetic keyword arguments of a weight gradient that stays on the fp32 / bf16-operand kernel
 # (filters, stride, residual) -- models/stgcn.py:113-123
 BLOCKS = [(64, 1, False), (64, 1, True), (64, 1, True), (64, 1, True), (128, 2, True), (128, 1, True), (128, 1, True),
           (256, 2, True), (256, 1, True), (256, 1, True)]
@@ -237,15 +239,17 @@ class STGCN(FlatEngine):
         """what the arithmetic needs beside the fp32 parameters: bf16 operand images (cn8: of EVERY conv weight), the split engines'
         term images and operand-bound cells, the fp32 engines' transposed data-gradient operands"""
         dev = self.device
-        self.packed = self.spacked = self._cells = None
+        self.packed = self.plan = self.spacked = self._cells = None
         if self.cn8:
             self.packed = self._pack(ops.PackedWeights(), lambda key, s, taps, Kc, M: True)
         if self.bf16:
             self.packed = self._pack(ops.PackedWeights(), lambda key, s, taps, Kc, M: M % 8 == 0 and Kc >= 16)
         if self.split:
-            self.spacked = self._pack(ops.PackedSplitWeights(self.split), self._split_admits)
-            # operand bounds of the fp16 arithmetic (include/sar_hip.h: cells), zeroed at the start of every training step
-            self._cells = torch.zeros(8 * len(self.blocks), dtype=torch.int32, device=dev)
+            # every per-launch decision of the split arithmetic, made here once (SAR_SPLIT_KINDS is read now, not per launch)
+            self.plan = SplitPlan(self, self._pack(ops.PackedSplitWeights(self.split), self._split_admits), _SPLIT_KINDS)
+            self.spacked, self._cells = self.plan.packed, self.plan.cells
+        # what block i's launches read (no plan: nothing on the split kernels)
+        self._recs = self.plan.blocks if self.plan else [BlockPlan(self._compact_skip(s)) for _, s, _ in self.blocks]
         # fp32 operands of the data-gradient GEMMs ((tap, f, c) / (k, f, c) / (f, c) transposes of the kernels): ONE
         # re-layout launch at the start of backward() instead of one small dependent launch in front of every data gradient
         # (22 per step, each on the critical chain)
@@ -403,18 +407,12 @@ class STGCN(FlatEngine):
                 # term images, bound cells and the Samuelson cells (functions of gamma / beta and the sample counts) beside the data_bn
                 # stage and the 3-channel layer: joined in front of the first launch that reads an image or a cell (_join_aux)
                 def images():
-                    self.spacked.refresh(self.flat)
-                    self._cells.zero_()
-                    Tb = T
-                    for bi_, (f_, s_, _r) in enumerate(self.blocks):
-                        if self._cell_live("l%d.tcn.f" % bi_, "tfwd", "twgrad"):
-                            ops.bn_bound(self.p["l%d.bn1.gamma" % bi_], self.p["l%d.bn1.beta" % bi_], B * Tb * V, self._cell(bi_, 0))
-                        Tb = same_pad(Tb, KT, s_)[0]
+                    self.plan.begin_step(self.flat)
+                    self.plan.raise_bn_bounds(B, T)
                 self._fork(images)      # behind the optimizer step that produced self.flat
                 self._aux_pending = self._bounds_forked = True
             else:
-                self.spacked.refresh(self.flat)
-                self._cells.zero_()
+                self.plan.begin_step(self.flat)
         # ---- data_bn (models/stgcn.py:142-147)
         part = None
         if training:
@@ -448,6 +446,7 @@ class STGCN(FlatEngine):
         To, pad, _ = same_pad(T, KT, s)
         n_in, n_out = B * T * V, B * To * V
         epi = L.SAR_EPI_STATS if training else L.SAR_EPI_NONE
+        rec = self._recs[i] if training else OFF      # inference keeps the fp32 kernels (no batch statistics to bound with)
         # sgcn: GraphConvTD (models/gcn.py:199-209)
         g = torch.empty((f, n_in), dtype=torch.float32, device=dev)
         y3 = None
@@ -457,44 +456,37 @@ class STGCN(FlatEngine):
                           M=KS * f, taps=1, stride=1, pad=0, bias=self.p[pre + "gcn.bias"])
             r1 = self._dense_fwd(i, y3, g, f, B, T, training)
         else:
-            gimg = self._simg(pre + "gcn.f") if training else None
-            if gimg is not None or (training and self._cell_live(pre + "gcn.f", "gfwd", "gwgrad")):
+            if rec.join_aux:
                 self._join_aux()                    # first reader of a term image / first writer of a cell on the main chain
-            if training and i == 0 and self._cell_live(pre + "gcn.f", "gfwd", "gwgrad"):
-                ops.amax(X, self._cell(i, 3))       # the bound of the block input (blocks > 0: written by the previous block's tail)
+            if rec.amax_X:
+                ops.amax(X, rec.X)                  # the bound of the block input (blocks > 0: written by the previous block's tail)
             r1 = ops.conv_gemm(L.SAR_CONV_GRAPH, X, g, self.p[pre + "gcn.kernel"], f, KS * f, B=B, V=V, T_src=T, T_out=T,
                                Kc=cin, M=f, taps=KS, bias=self.p[pre + "gcn.bias"], tables=self.tab_fwd, epi=epi,
-                               **self._split_args(gimg, self._cell(i, 3), self._img(pre + "gcn.f")))
+                               **self._arith(rec.gfwd, self._img(pre + "gcn.f")))
         bn1 = self._bn_forward(pre + "bn1", r1, n_in, training)
         # tgcn: BN -> ReLU folded into the operand load, Conv2D [9,1] stride s SAME (models/stgcn.py:26-36)
         u = torch.empty((f, n_out), dtype=torch.float32, device=dev)
-        simg = self._simg(pre + "tcn.f") if training else None        # inference keeps the fp32 kernels (no batch statistics to bound with)
         self._join_aux()           # (the 3-channel layer's graph convolution above reads neither images nor cells: the fork ends here)
-        if training and self._cell_live(pre + "tcn.f", "tfwd", "twgrad") and not self._bounds_forked:     # (a cell is raised when ANY split consumer of it is on)
-            ops.bn_bound(self.p[pre + "bn1.gamma"], self.p[pre + "bn1.beta"], n_in, self._cell(i, 0))
+        if rec.g is not None and not self._bounds_forked:
+            self.plan.raise_bn_bound(i, n_in)
         r2 = ops.conv_gemm(L.SAR_CONV_TEMPORAL, g, u, self.p[pre + "tcn.kernel"], f * f, f, B=B, V=V, T_src=T, T_out=To,
                            Kc=f, M=f, taps=KT, stride=s, pad=pad, bias=self.p[pre + "tcn.bias"],
-                           pro=(bn1.scale, bn1.shift), pro_relu=True, epi=epi,
-                           **self._split_args(simg, self._cell(i, 0), self._img(pre + "tcn.f")))
+                           pro=(bn1.scale, bn1.shift), pro_relu=True, epi=epi, **self._arith(rec.tfwd, self._img(pre + "tcn.f")))
         bn2 = self._bn_forward(pre + "bn2", r2, n_out, training)
         r = None
         rbn = None
         if kind == "conv":  # models/stgcn.py:47-56
             r = torch.empty((f, n_out), dtype=torch.float32, device=dev)
-            rsimg = self._simg(pre + "res.f") if training else None     # split arithmetic: X's bound is cell 3 (raised by the block below)
             r3 = ops.conv_gemm(L.SAR_CONV_TEMPORAL, X, r, self.p[pre + "res.kernel"], 0, f, B=B, V=V, T_src=T, T_out=To,
                                Kc=cin, M=f, taps=1, stride=s, pad=0, bias=self.p[pre + "res.bias"], epi=epi,
-                               **self._split_args(rsimg, self._cell(i, 3), self._img(pre + "res.f")))
+                               **self._arith(rec.rfwd, self._img(pre + "res.f")))
             rbn = self._bn_forward(pre + "res_bn", r3, n_out, training)
         y = torch.empty((f, n_out), dtype=torch.float32, device=dev)
         res_kind = {"none": 0, "identity": 1, "conv": 2}[kind]
         ymask = ops.relu_mask(y) if training else None     # 1 bit per element: what the BatchNorm-backward passes read instead of y
-        # (split arithmetic: y is the next block's graph-convolution operand; its bound is a by-product of this pass)
-        ycell = self._cell(i + 1, 3) if (training and i + 1 < len(self.blocks)
-                                         and (self._cell_live("l%d.gcn.f" % (i + 1), "gfwd", "gwgrad")
-                                              or self._cell_live("l%d.res.f" % (i + 1), "rfwd", "rwgrad"))) else None
+        # (split arithmetic: y is the next block's operand; its bound, rec.y, is a by-product of this pass)
         ops.bn_add_relu_fwd(u, bn2.scale, bn2.shift, res_kind, X if kind == "identity" else r,
-                            rbn.scale if rbn else None, rbn.shift if rbn else None, y, mask=ymask, amax_cell=ycell)
+                            rbn.scale if rbn else None, rbn.shift if rbn else None, y, mask=ymask, amax_cell=rec.y)
         if training:
             saved["blocks"].append(dict(X=X, g=g, u=u, r=r, y=y, ymask=ymask, T=T, To=To, pad=pad, cin=cin, f=f, s=s, kind=kind, y3=y3))
         if keep is not None:
@@ -536,39 +528,10 @@ class STGCN(FlatEngine):
         """packed bf16 operand image of a conv weight (bf16 mode), else None"""
         return self.packed.image(key) if self.packed is not None and key in self.packed.index else None
 
-    # ---- split arithmetic (mfma="f32_split*")
-    @property
-    def _f16(self):
-        return bool(self.split) and self.split.startswith("f16")
-
-    def _simg(self, key):
-        """(term images, w_bound cell) of a conv weight in split mode, else None"""
-        pk = self.spacked
-        kind = {"tcn.f": "tfwd", "tcn.b": "tdgrad", "gcn.f": "gfwd", "gcn.b": "gdgrad", "res.f": "rfwd", "res.b": "rdgrad"}[key.split(".", 1)[1]]
-        if kind not in _SPLIT_KINDS:
-            return None
-        return (pk.image(key), pk.bound(key)) if pk is not None and key in pk.index else None
-
-    def _cell_live(self, key, *kinds):
-        """does operand-bound cell of weight `key`'s layer have a split consumer that is switched on?  A cell is raised by its
-        producer whenever ANY of its consumers runs on the fp16 split kernels -- the forward launch or a weight gradient (ADVICE r05:
-        with SAR_SPLIT_KINDS=tdgrad,twgrad the weight gradient read a source bound that only the forward launch used to raise)."""
-        return bool(self._f16 and self._split_has(key) and any(k in _SPLIT_KINDS for k in kinds))
-
-    def _split_has(self, key):
-        """the split kernels take this conv weight's shape (its term images exist), whatever SAR_SPLIT_KINDS switches on"""
-        return self.spacked is not None and key in self.spacked.index
-
-    def _cell(self, i, j):
-        """operand-bound cell j of block i: 0 relu(bn1(g)), 1 du, 2 dg, 3 X, 4 dr"""
-        return self._cells[8 * i + j:8 * i + j + 1] if self._cells is not None else None
-
-    def _split_args(self, simg, src_cell, packed=None):
-        """the arithmetic keyword arguments of ops.conv_gemm: a launch on the split kernels (simg from _simg), else the fp32 /
-        bf16-operand kernel with its `packed` image"""
-        if simg is None:
-            return dict(split=None, bf16=self.bf16, packed=packed)
-        return dict(split=self.split, packed=simg[0], bounds=(src_cell, simg[1]))
+    def _arith(self, split_args, packed=None):
+        """the arithmetic keyword arguments of ops.conv_gemm: those of the block's record (sar_amd/split_plan.py) for a launch on the
+        split kernels, else the fp32 / bf16-operand kernel with its `packed` image"""
+        return split_args or dict(split=None, bf16=self.bf16, packed=packed)
 
     # ------------------------------------------------------------------ backward
     def _off_critical_path(self, fn, *tensors):
@@ -695,21 +658,17 @@ class STGCN(FlatEngine):
         du = torch.empty_like(u)
         dr = torch.empty_like(r) if kind == "conv" else None
         dz = dY if (kind == "identity" and gated is None) else None  # in place: dY becomes the pre-ReLU gradient for the skip path (already gated: nothing to write)
-        ducell = self._cell(i, 1) if self._cell_live(pre + "tcn.b", "tdgrad", "twgrad") else None   # the bound of du: by-product
-        # (the bound of dr: operand of the residual branch's dense 1x1 data gradient on conv_tap1_split_kernel; by-product too)
-        drcell = self._cell(i, 4) if (kind == "conv" and self._f16 and (
-            (self._simg(pre + "res.b") is not None and self._compact_skip(s, T, i)) or self._res_wgrad_split(pre))) else None
+        rec = self._recs[i]
+        # (the bounds of du and dr -- operands of the data and weight gradients below -- are by-products of the pass)
         ops.bn_add_relu_bwd_apply(dY, y, u, r if kind == "conv" else None, (bn2.k1, bn2.k2, bn2.k3), rk, du, dr, dz,
-                                  mask=sb.get("ymask"), amax_cell=ducell, amax_dr_cell=drcell)
+                                  mask=sb.get("ymask"), amax_cell=rec.du, amax_dr_cell=rec.dr)
         # ---- temporal conv: weight / bias gradient, then data gradient fused with ReLU-mask + BN1 reductions
         wt = self.g[pre + "tcn.kernel"]
         flat_w = self.grad[self.offsets[pre + "tcn.kernel"]:self.offsets[pre + "tcn.bias"] + f]
-        simg = self._simg(pre + "tcn.b")
         self._off_critical_path(lambda: ops.conv_wgrad(
             L.SAR_CONV_TEMPORAL, g, du, flat_w, B=B, V=V, T_src=T, T_out=To, Kc=f, M=f, taps=KT, stride=s, pad=pad,
             pro=(bn1.scale, bn1.shift), pro_relu=True, w_stride_tap=f * f, w_stride_c=f, wsize=wt.numel(), bsize=f,
-            bf16=self.bf16, split=self.split if ("twgrad" in _SPLIT_KINDS and self._split_has(pre + "tcn.f") and self._split_has(pre + "tcn.b")) else None,
-            bounds=(self._cell(i, 0), self._cell(i, 1)) if self._f16 else None, slabs=self._slabs), g, du)
+            bf16=self.bf16, slabs=self._slabs, **(rec.twgrad or _NO_SPLIT)), g, du)
         wimg = self._img(pre + "tcn.b")
         wT = None
         if wimg is None:
@@ -718,22 +677,18 @@ class STGCN(FlatEngine):
         dz1 = torch.empty((f, n_in), dtype=torch.float32, device=dev)
         pm = ops.conv_gemm(L.SAR_CONV_TEMPORAL, du, dz1, wT, f * f, f, B=B, V=V, T_src=To, T_out=T, Kc=f, M=f, taps=KT,
                            stride=s, pad=pad, transposed=True, epi=L.SAR_EPI_MASK, aux=g,
-                           aux_affine=(bn1.scale, bn1.shift), aux_mean=bn1.mean,
-                           **self._split_args(simg, self._cell(i, 1), wimg))
+                           aux_affine=(bn1.scale, bn1.shift), aux_mean=bn1.mean, **self._arith(rec.tdgrad, wimg))
         self._bn_backward(pre + "bn1", pm, 2, 1, n_in)
         dg = dz1
-        dgcell = self._cell(i, 2) if self._cell_live(pre + "gcn.b", "gdgrad", "gwgrad") else None      # the bound of dg: by-product
-        ops.affine2(dz1, g, (bn1.k1, bn1.k2, bn1.k3), dg, amax_cell=dgcell)   # BN1 backward apply (in place)
+        ops.affine2(dz1, g, (bn1.k1, bn1.k2, bn1.k3), dg, amax_cell=rec.dg)   # BN1 backward apply (in place; the bound of dg: by-product)
         flat_g = self.grad[self.offsets[pre + "gcn.kernel"]:self.offsets[pre + "gcn.bias"] + KS * f]
         if self.dense_A:
             return self._graph_backward_dense(i, sb, dg, dY, dr, B, flat_g), None
         # ---- graph conv: weight / bias gradient
-        gw_split = self.split if ("gwgrad" in _SPLIT_KINDS and self._split_has(pre + "gcn.f")
-                                  and self._split_has(pre + "gcn.b")) else None      # (both bounds exist: X from the forward, dg above)
         self._off_critical_path(lambda: ops.conv_wgrad(
             L.SAR_CONV_GRAPH, X, dg, flat_g, B=B, V=V, T_src=T, T_out=T, Kc=cin, M=f, taps=KS, tables=self.tab_fwd,
-            w_stride_tap=f, w_stride_c=KS * f, wsize=cin * KS * f, bsize=KS * f, bf16=self.bf16, split=gw_split,
-            bounds=(self._cell(i, 3), self._cell(i, 2)) if self._f16 else None, slabs=self._slabs), X, dg)
+            w_stride_tap=f, w_stride_c=KS * f, wsize=cin * KS * f, bsize=KS * f, bf16=self.bf16, slabs=self._slabs,
+            **(rec.gwgrad or _NO_SPLIT)), X, dg)
         dXres = self._residual_backward(i, sb, dr, B)
         # ---- graph conv data gradient (+ skip-path gradient)
         gimg = self._img(pre + "gcn.b")
@@ -743,18 +698,17 @@ class STGCN(FlatEngine):
             gT = self._wT[o:o + KS * f * cin]                             # [k][f][c]
         dX = torch.empty((cin, n_in), dtype=torch.float32, device=dev)
         aux = dY if kind == "identity" else dXres
-        even = kind == "conv" and aux is not None and self._compact_skip(s, T, i)   # dXres holds the even frames only
-        sgimg = self._simg(pre + "gcn.b")
+        even = kind == "conv" and aux is not None and rec.compact_skip   # dXres holds the even frames only
         if below is not None and aux is not None:
             # dX = gate_{i-1}(W^T dg . A^T + skip gradient) and block i - 1's BatchNorm-backward sums in one epilogue
             bn2b = self.bn["l%d.bn2" % (i - 1)]
             pm = ops.conv_gemm(L.SAR_CONV_GRAPH, dg, dX, gT, f * cin, cin, B=B, V=V, T_src=T, T_out=T, Kc=f, M=cin, taps=KS,
                                tables=self.tab_bwd, epi=L.SAR_EPI_ADD_GATE, aux=aux, aux2=below["u"], aux_mask=below["ymask"],
-                               aux_mean=bn2b.mean, aux_even_frames=even, **self._split_args(sgimg, self._cell(i, 2), None))
+                               aux_mean=bn2b.mean, aux_even_frames=even, **self._arith(rec.gdgrad))
             return dX, pm
         ops.conv_gemm(L.SAR_CONV_GRAPH, dg, dX, gT, f * cin, cin, B=B, V=V, T_src=T, T_out=T, Kc=f, M=cin, taps=KS,
                       tables=self.tab_bwd, epi=L.SAR_EPI_ADD if aux is not None else L.SAR_EPI_NONE, aux=aux, aux_even_frames=even,
-                      **self._split_args(sgimg, self._cell(i, 2), gimg))
+                      **self._arith(rec.gdgrad, gimg))
         return dX, None
 
     def _residual_backward(self, i, sb, dr, B):
@@ -764,11 +718,11 @@ class STGCN(FlatEngine):
         V, dev, pre = self.V, dr.device, "l%d." % i
         X, T, To, cin, f, s = sb["X"], sb["T"], sb["To"], sb["cin"], sb["f"], sb["s"]
         flat_r = self.grad[self.offsets[pre + "res.kernel"]:self.offsets[pre + "res.bias"] + f]
-        rw_split = self._res_wgrad_split(pre) and T == s * To      # wgrad_tap1_split_kernel: bounds = X's cell 3, dr's cell 4
+        rec = self._recs[i]
+        rwgrad = (rec.rwgrad if T == s * To else None) or _NO_SPLIT      # (wgrad_tap1_split_kernel takes whole strides only)
         self._off_critical_path(lambda: ops.conv_wgrad(
             L.SAR_CONV_TEMPORAL, X, dr, flat_r, B=B, V=V, T_src=T, T_out=To, Kc=cin, M=f, taps=1, stride=s, pad=0,
-            w_stride_tap=0, w_stride_c=f, wsize=cin * f, bsize=f, slabs=self._slabs, split=self.split if rw_split else None,
-            bounds=(self._cell(i, 3), self._cell(i, 4)) if (rw_split and self._f16) else None), X, dr)
+            w_stride_tap=0, w_stride_c=f, wsize=cin * f, bsize=f, slabs=self._slabs, **rwgrad), X, dr)
         rimg = self._img(pre + "res.b")
         rT = None
         if rimg is None and pre + "res" in self._wT_off:
@@ -777,31 +731,25 @@ class STGCN(FlatEngine):
         elif rimg is None:             # engines without the batched re-layout (ST-GIN)
             rT = torch.empty((f, cin), dtype=torch.float32, device=dev)
             ops.transpose(self.p[pre + "res.kernel"], rT, 1, cin, f)
-        if self._compact_skip(s, T, i):
+        if rec.compact_skip:
             # the gradient through a stride-2 1x1 convolution is non-zero on EVEN input frames only: a dense 1x1 product over the To
             # frames (half the matrix work of the strided data gradient, half the bytes written), added by the graph data gradient's
             # epilogue on even frames (SAR_GRAPH_AUX_EVEN_FRAMES) -- the zeros are neither written nor read back
             dXc = torch.empty((cin, B * To * V), dtype=torch.float32, device=dev)
-            rb = self._simg(pre + "res.b")
             ops.conv_gemm(L.SAR_CONV_TEMPORAL, dr, dXc, rT, 0, cin, B=B, V=V, T_src=To, T_out=To, Kc=f, M=cin, taps=1, stride=1, pad=0,
-                          **self._split_args(rb, self._cell(i, 4), None))
+                          **self._arith(rec.rdgrad))
             return dXc
         dXres = torch.empty((cin, B * T * V), dtype=torch.float32, device=dev)
         ops.conv_gemm(L.SAR_CONV_TEMPORAL, dr, dXres, rT, 0, cin, B=B, V=V, T_src=To, T_out=T, Kc=f, M=cin, taps=1,
                       stride=s, pad=0, transposed=True, bf16=self.bf16, packed=rimg)
         return dXres
 
-    def _res_wgrad_split(self, pre):
-        """the residual 1x1 convolution's weight gradient on wgrad_tap1_split_kernel: the layer has its forward term images (the same
-        shape test) and the kind is switched on"""
-        return bool(self.split in ("f16x3a", "bf16x6") and "rwgrad" in _SPLIT_KINDS and ops.TAP1_SPLIT and self._split_has(pre + "res.f"))
-
-    def _compact_skip(self, s, T, i=None):
+    def _compact_skip(self, s, split_product=False):
         """the skip gradient of a conv-residual block as its even frames only (SAR_COMPACT_SKIP=0: the strided data gradient over all
         T frames): fp32-storage engines with gather tables and fp32 / split arithmetic.  Default ("fp32"): the fp32 engine, and the
-        blocks of a split engine whose dense 1x1 product runs on conv_tap1_split_kernel (round 6)"""
-        on = _COMPACT_SKIP == "1" or (_COMPACT_SKIP == "fp32" and (not self.split or (
-            i is not None and self._simg("l%d.res.b" % i) is not None)))
+        blocks of a split engine whose dense 1x1 product runs on conv_tap1_split_kernel (round 6; split_product).  Static per block:
+        asked once, when the engine is built (BlockPlan.compact_skip)"""
+        on = _COMPACT_SKIP == "1" or (_COMPACT_SKIP == "fp32" and (not self.split or split_product))
         return on and s == 2 and not self.bf16 and not self.cn8 and not self.dense_A and self.stock_backward
 
     def _graph_backward_dense(self, i, sb, dg, dY, dr, B, flat_g):

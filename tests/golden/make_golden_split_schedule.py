@@ -1,0 +1,214 @@
+"""Writes tests/golden/split_schedule.json: the launch schedule of one fp32-storage ST-GCN train step on device="cpu", with the launch
+wrappers of sar_amd.ops replaced by recorders -- which conv_gemm / conv_wgrad launch takes which split arithmetic, which operand-bound
+cell, term image and weight bound it is handed, and which pass raises which cell, in issue order -- for both split arithmetics times every subset of the nine kernel
+kinds of SAR_SPLIT_KINDS.  Run at the commit whose schedule is the reference: the fixture pins it for every later restructuring of the
+step's host code, so it is never regenerated from the code under test (tests/test_split_schedule.py imports trace() from here).
+Uses only the public wrappers of sar_amd.ops, stgcn._SPLIT_KINDS and the engine's `packed` / `spacked`."""
+import hashlib
+import itertools
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+for _p in (ROOT, os.path.join(ROOT, "skeleton-action-recognition_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import torch  # noqa: E402
+
+KINDS = ("tfwd", "tdgrad", "twgrad", "gfwd", "gdgrad", "gwgrad", "rfwd", "rdgrad", "rwgrad")
+SPLIT_MODES = ("f32_split", "f32_split_bf16x6")
+BLOCKS = [(64, 1, False), (64, 1, True), (128, 2, True), (128, 1, True)]
+CLIP = (1, 3, 12, 25, 2)
+# the switch values whose full trace the fixture holds for reading (and that tests/test_gpu_split.py runs on the GPU)
+NAMED = ("tdgrad,twgrad", "gfwd,gwgrad", "rfwd,rdgrad,rwgrad", "tfwd,gdgrad,rwgrad", ",".join(KINDS), "")
+FULL_TRACES = (("f32_split", ",".join(KINDS)), ("f32_split", "tdgrad,twgrad"), ("f32_split", "rfwd,rdgrad,rwgrad"),
+               ("f32_split_bf16x6", ",".join(KINDS)))
+# wrappers a step calls that launch one kernel and return nothing
+_SILENT = ("bn_finalize", "bn_eval_affine", "bn_bwd_finalize", "data_bn_stats", "data_bn_apply", "data_bn_bwd_reduce", "pool_fwd",
+           "fc_fwd", "softmax_ce", "fc_bwd", "pool_bwd", "transpose")
+
+
+class _Clip(torch.Tensor):
+    """a CPU tensor that forward() takes for a device one"""
+    is_cuda = property(lambda self: True)
+
+
+def subsets():
+    """every subset of KINDS as a tuple in KINDS' order, by size"""
+    for n in range(len(KINDS) + 1):
+        yield from itertools.combinations(KINDS, n)
+
+
+def key(mode, kinds):
+    return "%s|%s" % (mode, ",".join(kinds))
+
+
+class Recorder:
+    """stands in for the launch wrappers of sar_amd.ops while one step is driven; .trace is the schedule"""
+
+    def __init__(self, ops, L, eng):
+        self.ops, self.L, self.trace, self._names, self._saved = ops, L, [], {}, {}
+        # what a launch was handed, by address: the operand images and the weight bounds of the engine's packed weights
+        self._images, self._w_bounds = {}, {}
+        for tag, pk in (("bf16", eng.packed), ("split", eng.spacked)):
+            for k in (pk.index if pk is not None else ()):
+                self._images[pk.image(k).data_ptr()] = "%s:%s" % (tag, k)
+        for k in (eng.spacked.index if eng.spacked is not None else ()):
+            self._w_bounds[eng.spacked.bound(k).data_ptr()] = "w:" + k
+
+    def cell(self, c):
+        """cells are named by order of first appearance"""
+        return None if c is None else self._names.setdefault(c.data_ptr(), "c%d" % len(self._names))
+
+    def raised(self, by, cell):
+        if cell is not None:
+            self.trace.append({"raise": by, "cell": self.cell(cell)})
+
+    # ---- the recorders
+    def amax(self, x, cell):
+        self.raised("amax", cell)
+
+    def bn_bound(self, gamma, beta, count, cell):
+        self.raised("bn_bound", cell)
+
+    def bn_add_relu_fwd(self, u, sc, sh, res_kind, r, rsc, rsh, y, mask=None, amax_cell=None):
+        self.raised("bn_add_relu_fwd", amax_cell)
+
+    def bn_add_relu_bwd_apply(self, dy, y, u, r, k, rk, du, dr, dz_out, mask=None, amax_cell=None, amax_dr_cell=None):
+        self.raised("bn_add_relu_bwd_apply", amax_cell)
+        self.raised("bn_add_relu_bwd_apply.dr", amax_dr_cell if dr is not None else None)
+
+    def affine2(self, a, b, k, out, amax_cell=None):
+        self.raised("affine2", amax_cell)
+
+    def bn_add_relu_bwd_reduce(self, dy, y, u, r, mu=None, mr=None, tail=None, mask=None):
+        return torch.empty((u.shape[0], 1, 4)), 1
+
+    def conv_gemm(self, mode, src, out, W, w_stride_tap, w_stride_c, *, B, V, T_src, T_out, Kc, M, taps, stride=1, pad=0,
+                  transposed=False, bias=None, pro=None, pro_relu=False, tables=None, epi=0, aux=None, aux_affine=None, aux_mean=None,
+                  bf16=False, packed=None, partials_out=None, aux2=None, aux_mask=None, split="default", bounds=None,
+                  aux_even_frames=False):
+        ops, L = self.ops, self.L
+        if split == "default":
+            split = ops.DEFAULT_SPLIT
+        # the wrapper's own demotion rule
+        split = split if (split and ops.split_applicable(mode, V, Kc, M, taps, stride, tables, pro, transposed, pad)
+                          and (epi != L.SAR_EPI_ADD_GATE or mode == L.SAR_CONV_GRAPH)) else None
+        if split and (mode == L.SAR_CONV_GRAPH or taps == 1) and split not in ("bf16x6", "f16x3a"):
+            split = None
+        rec = dict(op="conv_gemm", mode=mode, taps=taps, transposed=bool(transposed), Kc=Kc, M=M, stride=stride, epi=epi, split=split,
+                   packed=None if packed is None else self._images.get(packed.data_ptr(), "?"),
+                   bf16=bool(bf16 and not split and M % 8 == 0 and Kc >= 16), even=bool(aux_even_frames))
+        if split and split.startswith("f16"):      # (source cell, the weight's bound by the key of its image)
+            rec["bounds"] = [self.cell(bounds[0]), self._w_bounds.get(bounds[1].data_ptr(), "?")] if bounds is not None else None
+        self.trace.append(rec)
+        if epi in (L.SAR_EPI_STATS, L.SAR_EPI_MASK, L.SAR_EPI_ADD_GATE):
+            return torch.empty((M, 1, 2)), 1
+        return None
+
+    def conv_wgrad(self, mode, src, dout, dW_out, *, B, V, T_src, T_out, Kc, M, taps, stride=1, pad=0, pro=None, pro_relu=False,
+                   tables=None, w_stride_tap, w_stride_c, wsize, bsize, nsplit=None, bf16=False, split="default", bounds=None,
+                   slabs=None):
+        ops, L = self.ops, self.L
+        if split == "default":
+            split = ops.DEFAULT_SPLIT
+        if taps == 1 and mode == L.SAR_CONV_TEMPORAL and not ops.TAP1_SPLIT:
+            split = None
+        rec = dict(op="conv_wgrad", mode=mode, taps=taps, transposed=False, Kc=Kc, M=M, stride=stride, epi=None, split=split,
+                   packed=None, bf16=bool(bf16 and not split))
+        if split and split.startswith("f16"):
+            rec["bounds"] = [self.cell(c) for c in bounds] if bounds is not None else None
+        self.trace.append(rec)
+
+    # ---- installation
+    def __enter__(self):
+        ops = self.ops
+        put = {n: (lambda *a, **k: None) for n in _SILENT}
+        put.update({n: getattr(self, n) for n in ("amax", "bn_bound", "bn_add_relu_fwd", "bn_add_relu_bwd_apply", "affine2",
+                                                  "bn_add_relu_bwd_reduce", "conv_gemm", "conv_wgrad")})
+        for n, fn in put.items():
+            self._saved[(ops, n)] = getattr(ops, n)
+            setattr(ops, n, fn)
+        for cls, n in ((ops.PackedWeights, "refresh"), (ops.PackedSplitWeights, "refresh"), (ops.PermuteBatch, "run")):
+            self._saved[(cls, n)] = cls.__dict__[n]
+            setattr(cls, n, lambda self_, *a, **k: None)
+        return self
+
+    def __exit__(self, *exc):
+        for (owner, n), fn in self._saved.items():
+            setattr(owner, n, fn)
+        return False
+
+
+def trace(mode, kinds=None):
+    """the schedule of one forward(training=True) + backward() of the four-block engine in arithmetic `mode`; kinds: the value of
+    stgcn._SPLIT_KINDS the engine is built and run under (None: as the module has it)"""
+    from sar_amd import _lib as L
+    from sar_amd import ops, stgcn
+    old = stgcn._SPLIT_KINDS
+    if kinds is not None:
+        stgcn._SPLIT_KINDS = set(kinds)
+    try:
+        eng = stgcn.STGCN(device="cpu", num_classes=7, mfma=mode, blocks=BLOCKS)
+        with Recorder(ops, L, eng) as rec:
+            logits = eng.forward(torch.zeros(CLIP).as_subclass(_Clip), training=True)
+            eng.backward(torch.zeros_like(logits))
+    finally:
+        stgcn._SPLIT_KINDS = old
+    return rec.trace
+
+
+def digest(tr):
+    """three hex digits per entry of the trace, in order: two digests differ first at the first entry that differs"""
+    return "".join(hashlib.sha256(json.dumps(ev, sort_keys=True).encode()).hexdigest()[:3] for ev in tr)
+
+
+def first_difference(got, want):
+    """index of the first trace entry at which two digests differ (the shorter one's length when one is a prefix of the other)"""
+    n = min(len(got), len(want)) // 3
+    return next((k for k in range(n) if got[3 * k:3 * k + 3] != want[3 * k:3 * k + 3]), n)
+
+
+def check_invariants(tr):
+    """every cell an fp16 split launch reads was raised earlier in the step; no raised cell goes unread.  Returns a list of complaints."""
+    raised, read, bad = set(), set(), []
+    for n, ev in enumerate(tr):
+        if "raise" in ev:
+            raised.add(ev["cell"])
+        elif "bounds" in ev:
+            if ev["bounds"] is None or None in ev["bounds"]:
+                bad.append("launch %d (%s) runs an fp16 split arithmetic without its bound cells" % (n, ev))
+                continue
+            for c in ev["bounds"]:
+                if c.startswith("w:"):      # a weight's bound comes with its term images (one pack launch per step)
+                    continue
+                if c == "?":
+                    bad.append("launch %d (%s) was handed a weight bound that is none of the engine's" % (n, ev))
+                    continue
+                read.add(c)
+                if c not in raised:
+                    bad.append("launch %d (%s) reads cell %s, which nothing raised before it" % (n, ev, c))
+    bad += ["cell %s is raised and never read" % c for c in sorted(raised - read)]
+    return bad
+
+
+if __name__ == "__main__":
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    digests, full = {}, {}
+    for mode in SPLIT_MODES:
+        for ks in subsets():
+            tr = trace(mode, ks)
+            assert not check_invariants(tr), (mode, ks, check_invariants(tr))
+            digests[key(mode, ks)] = digest(tr)
+    for mode, ks in FULL_TRACES:
+        full["%s|%s" % (mode, ks)] = trace(mode, [k for k in ks.split(",") if k])
+    for mode in ("fp32", "bf16_operands"):
+        digests[key(mode, ("default",))] = digest(trace(mode))
+    with open(os.path.join(HERE, "split_schedule.json"), "w") as fh:
+        fh.write('{"digests": {\n' + ",\n".join("%s: %s" % (json.dumps(k), json.dumps(v)) for k, v in digests.items()) + '\n},\n'
+                 + '"traces": {\n' + ",\n".join("%s: [\n  %s\n]" % (json.dumps(k), ",\n  ".join(json.dumps(e, sort_keys=True) for e in v))
+                                               for k, v in full.items()) + "\n}}\n")
+    print("wrote %d digests, %d full traces" % (len(digests), len(full)))
