@@ -23,6 +23,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .engine import FlatEngine
+from .split_plan import ResNetPlan
 from .stgcn import _BN, SPLIT_ARITH
 
 BN_EPS = 1e-5            # torch BatchNorm2d defaults (models/resnet18.py norm_layer = nn.BatchNorm2d)
@@ -32,6 +33,7 @@ LAYERS = [2, 2, 2, 2]    # models/resnet18.py:274
 # "fp32" = fp32 MFMA kernels; "f32_split" / "f32_split_bf16x6" = fp32 results on the fp16 / bf16 matrix pipe for the 3x3 / stride-1
 # convolutions (csrc/conv2d_split.hip), everything else unchanged
 DEFAULT_MFMA = os.environ.get("SAR_MFMA_PATHB", "fp32")
+# which kernel families of a split engine ask for the split kernels: read when an engine is constructed (sar_amd/split_plan.py)
 _SPLIT_KINDS = set(os.environ.get("SAR_SPLIT_KINDS_PATHB", "fwd,dgrad,wgrad").split(","))
 
 
@@ -145,27 +147,11 @@ class ResNet18(FlatEngine):
         pb.finalize(dev)
         self._perm_bwd = pb
         self._wb = torch.zeros(off, dtype=torch.float32, device=dev)
-        # Split arithmetic: the term images of every 3x3 / stride-1 weight tensor -- forward view (tap, c, m) and data-gradient view
-        # (mirrored taps, c and m exchanged: include/sar_hip.h sar_conv2d_gemm_split) -- written by ONE launch per step from the
-        # master weights, and the bound cells of the source operands (zeroed once per step; raised by the producing passes)
-        self.spacked, self._cells, self._cell_of = None, None, {}
-        if self.split and dev.type == "cuda":
-            sp = ops.PackedSplitWeights(self.split)
-            for name, cv in self.convs.items():
-                if cv.k == 3 and cv.stride == 1 and 8 <= cv.cin <= 512 and cv.cout % 8 == 0 and cv.cout <= 512:
-                    src, cc = self.offsets[name + ".weight"], cv.cin * cv.cout
-                    sp.add((name, "f"), src, cc, cv.cout, 1, 9, cv.cin, cv.cout)
-                    sp.add((name, "b"), src + 8 * cc, -cc, 1, cv.cout, 9, cv.cout, cv.cin)
-                    for kind in ("f", "b"):
-                        self._cell_of[(name, kind)] = len(self._cell_of)
-                elif cv.k == 3 and cv.stride == 2 and 8 <= cv.cin and cv.cin % 8 == 0 and 16 <= cv.cout <= 512:
-                    # the stride-2 data gradient (four parity classes, csrc/conv2d_split.hip): the forward taps of the (tap, m, c) view
-                    src, cc = self.offsets[name + ".weight"], cv.cin * cv.cout
-                    sp.add((name, "b"), src, cc, 1, cv.cout, 9, cv.cout, cv.cin)
-                    self._cell_of[(name, "b")] = len(self._cell_of)
-            sp.finalize(dev)
-            self.spacked = sp
-            self._cells = torch.zeros(max(1, len(self._cell_of)), dtype=torch.int32, device=dev)
+        # Split arithmetic: the term images of the 3x3 weight tensors -- written by ONE launch per step from the master weights --, the
+        # bound cells of the source operands (zeroed once per step; raised by the producing passes) and every per-launch decision,
+        # made here once (SAR_SPLIT_KINDS_PATHB is read now, not per launch).  An fp32 engine's plan has every record on the fp32 kernels
+        self.plan = ResNetPlan(self, _SPLIT_KINDS)
+        self.spacked = self.plan.packed
 
     def _make_buckets(self, total):
         """Gradient buckets for the data-parallel exchange (main_spectrogram.py:118-119), in the order backward() completes them:
@@ -220,10 +206,8 @@ class ResNet18(FlatEngine):
     # ------------------------------------------------------------------ weights
     def _pack(self, need_bwd):
         """(tap, m, c) data-gradient layout of every conv weight: one launch per training step."""
-        if need_bwd and self.spacked is not None:
-            self.spacked.refresh(self.flat)
-            self._cells.zero_()
         if need_bwd:            # only the backward pass reads the data-gradient layouts: off the forward's critical path
+            self.plan.begin_step(self.flat)
             self._on_side(lambda: self._perm_bwd.run(self.flat, self._wb))      # after the optimizer step that produced self.flat
             if self._side is not None:
                 self._wb_ready = torch.cuda.Event()
@@ -245,56 +229,19 @@ class ResNet18(FlatEngine):
         o, n = self.offsets[name + ".weight"], self._woff[name][1]
         return self.flat[o:o + n]                      # the stored weights ARE the forward operand
 
-    def _cell(self, name, kind):
-        """bound cell of the source operand of conv `name`'s forward ("f") / data gradient ("b") on the split kernels, else None"""
-        i = self._cell_of.get((name, kind)) if self._cells is not None else None
-        return None if i is None else self._cells[i:i + 1]
-
-    def _split_args(self, name, kind, training=True):
-        """arithmetic keyword arguments of ops.conv2d_gemm for conv `name` (training steps only: inference keeps the fp32 kernels)"""
-        want = {"f": "fwd", "b": "dgrad"}[kind] in _SPLIT_KINDS
-        if not training or self.spacked is None or (name, kind) not in self._cell_of or not want:
-            return dict(split=None)
-        return dict(split=self.split, packed=self.spacked.image((name, kind)),
-                    bounds=(self._cell(name, kind), self.spacked.bound((name, kind))))
-
-    def _conv_fwd(self, name, X, B, H, W, training, pro=None, bn_src=None, out=None):
-        """bn_src: (BatchNorm name, sample count) of the folded prologue -- the source bound of the split kernels is then the Samuelson
-        bound of that train-mode BatchNorm (no pass over the data); without a prologue the producer of X has raised the cell."""
+    def _conv_fwd(self, name, X, B, H, W, training, pro=None, out=None):
+        """the source bound of the split kernels: without a prologue the producer of X has raised the cell; behind a folded train-mode
+        BatchNorm it is that BatchNorm's Samuelson bound (self.plan.bounds: no pass over the data)"""
         cv = self.convs[name]
         Ho, Wo = (H + 2 * cv.pad - cv.k) // cv.stride + 1, (W + 2 * cv.pad - cv.k) // cv.stride + 1
         if out is None:
             out = torch.empty((cv.cout, B * Ho * Wo), dtype=torch.float32, device=X.device)
         assert out.shape == (cv.cout, B * Ho * Wo)
-        sa = self._split_args(name, "f", training)
-        # (raised whenever the cell exists: the forward launch AND the weight gradient read it -- ADVICE r05: with
-        # SAR_SPLIT_KINDS_PATHB=dgrad,wgrad the weight gradient read a bound that only a split forward launch used to raise)
-        if training and bn_src is not None and self._cell(name, "f") is not None and not self._bounds_forked:
-            ops.bn_bound(self.p[bn_src[0] + ".weight"], self.p[bn_src[0] + ".bias"], bn_src[1], self._cell(name, "f"))
         r = ops.conv2d_gemm(X, out, self._w(name), cv.cin * cv.cout, cv.cout,
                             epi=L.SAR_EPI_STATS if training else L.SAR_EPI_NONE, B=B, Kc=cv.cin, M=cv.cout, H_src=H,
                             W_src=W, H_out=Ho, W_out=Wo, KH=cv.k, KW=cv.k, stride=cv.stride, pad=cv.pad, pro=pro,
-                            pro_relu=pro is not None, **sa)
+                            pro_relu=pro is not None, **self.plan.rec(name, training).fwd)
         return out, r, Ho, Wo
-
-    def _all_bn_bounds(self, B, H, W):
-        """the Samuelson bound cells of a training step -- the stem's (source of the first block) and every block's bn1 (folded into
-        conv2's operand) -- from the geometry alone: what forward() raises layer by layer when they are not forked"""
-        def osz(n, cv):
-            return (n + 2 * cv.pad - cv.k) // cv.stride + 1
-        cv = self.convs["conv1"]
-        H1, W1 = osz(H, cv), osz(W, cv)
-        first = self._cell(self.blocks[0][0] + "conv1", "f")
-        if first is not None:
-            ops.bn_bound(self.p["bn1.weight"], self.p["bn1.bias"], B * H1 * W1, first)
-        Hc, Wc = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
-        for pre, inpl, planes, stride, ds in self.blocks:
-            c1 = self.convs[pre + "conv1"]
-            Ho, Wo = osz(Hc, c1), osz(Wc, c1)
-            cell = self._cell(pre + "conv2", "f")
-            if cell is not None:
-                ops.bn_bound(self.p[pre + "bn1.weight"], self.p[pre + "bn1.bias"], B * Ho * Wo, cell)
-            Hc, Wc = Ho, Wo
 
     def _bn_stats(self, name, r, count, training):
         b = self.bn[name]
@@ -319,12 +266,13 @@ class ResNet18(FlatEngine):
         if not join_aux:
             self._pack(training)
         self._prepacked = None
+        plan = self.plan
         self._bounds_forked = False
-        if training and self._aux is not None and self._cells is not None:
+        if training and self._aux is not None and plan.cells is not None:
             # every Samuelson bound of the step (they depend on gamma / beta and the sample counts only) on the third stream, beside
             # the stem: nine 4-us launches off the serial chain; joined in front of the first block.  Behind the zeroing of the cells:
             # prepacked, they were zeroed on that stream
-            self._fork(lambda: self._all_bn_bounds(B, H, W), after="nothing" if join_aux else "main")
+            self._fork(lambda: plan.raise_bn_bounds(B, H, W), after="nothing" if join_aux else "main")
             self._bounds_forked = join_aux = True
         X0 = x.view(1, B * H * W)
         c0, r, H1, W1 = self._conv_fwd("conv1", X0, B, H, W, training)
@@ -338,12 +286,10 @@ class ResNet18(FlatEngine):
         Hc, Wc = H2, W2
         if join_aux:
             self._join()
-        if self._bounds_forked:
-            pass
-        elif training and self._cell(self.blocks[0][0] + "conv1", "f") is not None:
-            # the stem tail is max-pool(relu(bn1(c0))): bounded by bn1's Samuelson bound
-            ops.bn_bound(self.p["bn1.weight"], self.p["bn1.bias"], B * H1 * W1, self._cell(self.blocks[0][0] + "conv1", "f"))
-        for bi_, (pre, inpl, planes, stride, ds) in enumerate(self.blocks):
+        if not self._bounds_forked:      # the stem tail is max-pool(relu(bn1(c0))): bounded by bn1's Samuelson bound
+            plan.raise_bn_bound(plan.rec(self.blocks[0][0] + "conv1", training).bound, B * H1 * W1)
+        for pre, inpl, planes, stride, ds in self.blocks:
+            rec2 = plan.rec(pre + "conv2", training)
             dsc, bd = None, self.bn.get(pre + "downsample.1")
             forked = ds and self._aux is not None
             def branch(out=None):
@@ -357,8 +303,9 @@ class ResNet18(FlatEngine):
                 self._fork(lambda: branch(dsc), h)
             c1, r1, Ho, Wo = self._conv_fwd(pre + "conv1", h, B, Hc, Wc, training)
             b1 = self._bn_stats(pre + "bn1", r1, B * Ho * Wo, training)
-            c2, r2, _, _ = self._conv_fwd(pre + "conv2", c1, B, Ho, Wo, training, pro=(b1.scale, b1.shift),
-                                          bn_src=(pre + "bn1", B * Ho * Wo))
+            if not self._bounds_forked:
+                plan.raise_bn_bound(rec2.bound, B * Ho * Wo)
+            c2, r2, _, _ = self._conv_fwd(pre + "conv2", c1, B, Ho, Wo, training, pro=(b1.scale, b1.shift))
             b2 = self._bn_stats(pre + "bn2", r2, B * Ho * Wo, training)
             if forked:
                 self._join()
@@ -366,10 +313,8 @@ class ResNet18(FlatEngine):
                 dsc = branch()
             y = torch.empty_like(c2)
             ymask = ops.relu_mask(y) if training else None  # 1 bit per element: what the BatchNorm-backward passes read instead of y
-            nxt = self.blocks[bi_ + 1][0] + "conv1" if bi_ + 1 < len(self.blocks) else None
             ops.bn_add_relu_fwd(c2, b2.scale, b2.shift, 2 if ds else 1, dsc if ds else h, bd.scale if ds else None,
-                                bd.shift if ds else None, y, mask=ymask,
-                                amax_cell=self._cell(nxt, "f") if (training and nxt) else None)   # the next block's source bound
+                                bd.shift if ds else None, y, mask=ymask, amax_cell=rec2.y)   # the next block's source bound
             if training:
                 saved["blocks"].append(dict(X=h, c1=c1, c2=c2, dsc=dsc, y=y, ymask=ymask, H=Hc, W=Wc, Ho=Ho, Wo=Wo))
             if keep is not None:
@@ -390,13 +335,10 @@ class ResNet18(FlatEngine):
         cv = self.convs[name]
         o, n = self.offsets[name + ".weight"], self._woff[name][1]
 
-        sa = dict(split=None)      # split kernels: the source bound is the forward's cell, the dout bound the data gradient's
-        if self.spacked is not None and (name, "f") in self._cell_of and "wgrad" in _SPLIT_KINDS:
-            sa = dict(split=self.split, bounds=(self._cell(name, "f"), self._cell(name, "b")))
-
-        def run():
+        def run():      # (split kernels: the source bound is the forward's cell, the dout bound the data gradient's)
             ops.conv2d_wgrad(X, dout, self.grad[o:o + n], B=B, Kc=cv.cin, M=cv.cout, H_src=H, W_src=W, H_out=Ho, W_out=Wo, KH=cv.k,
-                             KW=cv.k, stride=cv.stride, pad=cv.pad, pro=pro, pro_relu=pro is not None, slabs=self._slabs, **sa)
+                             KW=cv.k, stride=cv.stride, pad=cv.pad, pro=pro, pro_relu=pro is not None, slabs=self._slabs,
+                             **self.plan.recs[name].wgrad)
         self._on_side(run, X, dout)
 
     def _conv_dgrad(self, name, dout, B, H, W, Ho, Wo, **epi):
@@ -405,7 +347,7 @@ class ResNet18(FlatEngine):
         dx = torch.empty((cv.cin, B * H * W), dtype=torch.float32, device=dout.device)
         r = ops.conv2d_gemm(dout, dx, self._w(name, True), cv.cout * cv.cin, cv.cin, B=B, Kc=cv.cout, M=cv.cin, H_src=Ho,
                             W_src=Wo, H_out=H, W_out=W, KH=cv.k, KW=cv.k, stride=cv.stride, pad=cv.pad, transposed=True,
-                            ctx=self._ctx, **self._split_args(name, "b"), **epi)
+                            ctx=self._ctx, **self.plan.recs[name].dgrad, **epi)
         return dx, r
 
     def _bn_bwd(self, name, part, nparts, chan_stride, part_stride, off2, count):
@@ -448,6 +390,7 @@ class ResNet18(FlatEngine):
             H, W, Ho, Wo = sb["H"], sb["W"], sb["Ho"], sb["Wo"]
             n_out = B * Ho * Wo
             b1, b2 = self.bn[pre + "bn1"], self.bn[pre + "bn2"]
+            rec1, rec2 = self.plan.recs[pre + "conv1"], self.plan.recs[pre + "conv2"]
             bd = self.bn.get(pre + "downsample.1")
             rk = (bd.k1, bd.k2, bd.k3) if ds else None
             if ops.BN_TAIL or BN_TAIL_PATHB == "1" or (BN_TAIL_PATHB == "split" and self.split):   # the reduce kernel's last workgroup per channel finalises bn2 (and the downsample BN)
@@ -468,7 +411,7 @@ class ResNet18(FlatEngine):
             dc2 = torch.empty_like(c2)
             ddsc = torch.empty_like(dsc) if ds else None
             ops.bn_add_relu_bwd_apply(dY, y, c2, dsc, (b2.k1, b2.k2, b2.k3), rk, dc2, ddsc, None if ds else dY, mask=sb.get("ymask"),
-                                      amax_cell=self._cell(pre + "conv2", "b"))      # bound of dc2 for conv2's split data gradient
+                                      amax_cell=rec2.b)      # bound of dc2 for conv2's split data gradient
             # the 1x1 / stride 2 data gradient is non-zero at the even pixels only: computed at the small resolution (a plain stride-1
             # product) and added there by the parity-class launches of conv1's data gradient.  Its output is allocated HERE, in front
             # of the event its fork waits for: the third stream may write it before the main stream's later launches have run, so the
@@ -485,7 +428,7 @@ class ResNet18(FlatEngine):
             dz1, pm = self._conv_dgrad(pre + "conv2", dc2, B, Ho, Wo, Ho, Wo, epi=L.SAR_EPI_MASK, aux=c1,
                                        aux_affine=(b1.scale, b1.shift), aux_mean=b1.mean)
             self._bn_bwd(pre + "bn1", pm[0], pm[1], pm[1] * 2, 2, 1, n_out)
-            ops.affine2(dz1, c1, (b1.k1, b1.k2, b1.k3), dz1, amax_cell=self._cell(pre + "conv1", "b"))      # dc1 in place (+ its bound)
+            ops.affine2(dz1, c1, (b1.k1, b1.k2, b1.k3), dz1, amax_cell=rec1.b)      # dc1 in place (+ its bound)
             self._conv_wgrad(pre + "conv1", X, dz1, B, H, W, Ho, Wo)
             if ds:
                 self._conv_wgrad(pre + "downsample.0", X, ddsc, B, H, W, Ho, Wo)

@@ -18,7 +18,10 @@ with its term images; the five activation operands of a block have a cell each, 
   dr    gradient of the residual conv   the backward tail pass                             rdgrad, rwgrad
 
 A cell exists -- and is raised -- exactly when at least one of its consumers is ON (_CONSUMERS below is the one place that says so);
-otherwise the record holds None and the producer's `amax_cell=None` raises nothing.  The bf16x6 arithmetic scales nothing: no cells."""
+otherwise the record holds None and the producer's `amax_cell=None` raises nothing.  The bf16x6 arithmetic scales nothing: no cells.
+
+ResNetPlan, below, is the same for Path B's classifier (sar_amd/resnet.py): one record per convolution; its docstring has that engine's
+table, and the one rule it does NOT share with the plan above."""
 import torch
 
 from . import ops
@@ -113,3 +116,131 @@ class SplitPlan:
             if self.blocks[i].g is not None:
                 self.raise_bn_bound(i, B * T * self.V)
             T = -(-T // s)
+
+
+# ---------------------------------------------------------------------------------------------------- Path B's classifier
+_FP32 = dict(split=None)
+
+
+def _views(cv):
+    """the term images a convolution gets -- the one place that says so: "f" = the forward view (tap, c, m), "b" = the data-gradient
+    view (c and m exchanged).  3x3 / stride 1: both; 3x3 / stride 2: the data gradient's (four parity classes, csrc/conv2d_split.hip)"""
+    if cv.k == 3 and cv.stride == 1 and 8 <= cv.cin <= 512 and cv.cout % 8 == 0 and cv.cout <= 512:
+        return ("f", "b")
+    if cv.k == 3 and cv.stride == 2 and 8 <= cv.cin and cv.cin % 8 == 0 and 16 <= cv.cout <= 512:
+        return ("b",)
+    return ()
+
+
+class ConvPlan:
+    """One convolution's record; plain attributes, fixed at construction.  The default is a convolution on the fp32 kernels.
+      fwd dgrad   keyword arguments of ops.conv2d_gemm: dict(split=None), or dict(split=, packed=, bounds=(f / b, w_bound))
+      wgrad       keyword arguments of ops.conv2d_wgrad: dict(split=None), or dict(split=, bounds=(f, b))
+      f b         the cell (one-element view) of the forward's / the data gradient's source operand, or None
+      y           on a block's conv2: the f cell of the NEXT block's conv1, raised by this block's tail
+      bound       index into ResNetPlan.bounds of the Samuelson bound that raises f, or None"""
+    __slots__ = ("fwd", "dgrad", "wgrad", "f", "b", "y", "bound")
+
+    def __init__(self):
+        self.fwd = self.dgrad = self.wgrad = _FP32
+        self.f = self.b = self.y = self.bound = None
+
+
+CONV_OFF = ConvPlan()
+
+
+class ResNetPlan:
+    """What a ResNet18 engine (sar_amd/resnet.py) decides once, when it is constructed.  packed: the PackedSplitWeights (None:
+    mfma="fp32"); cells: the int32 cell tensor; recs: one ConvPlan per convolution name; bounds: the Samuelson bounds of a step as
+    (gamma, beta, cell, the convolution whose output the BatchNorm normalises -- its sample count), in the order they are raised.
+
+    The kinds of SAR_SPLIT_KINDS_PATHB are fwd, dgrad, wgrad.  A launch ASKS for the split kernels when its kind is switched on and
+    its term image exists (_views; a weight gradient: the "f" image); the wrapper still demotes it at a feature map the kernels are
+    not built for (ops.conv2d_split_applicable: at a (2, 1, 64, 64) clip every launch of layers 3 and 4).
+
+      cell      bounds                          raised by                                                read by
+      conv1.f   the block input                 block 0: ops.bn_bound of the stem's bn1 (the stem tail   conv1 fwd, conv1 wgrad
+                                                is max-pool(relu(bn1))); else the tail of the block
+                                                below (bn_add_relu_fwd, that block's conv2 record: y)
+      conv2.f   relu(bn1(conv1 output))         ops.bn_bound of the block's bn1, folded into conv2's     conv2 fwd, conv2 wgrad
+                                                operand load (Samuelson: no pass over the data)
+      conv2.b   gradient of conv2's output      the backward tail pass (bn_add_relu_bwd_apply)           conv2 dgrad, conv2 wgrad
+      conv1.b   gradient of conv1's output      the BN1-backward apply pass (affine2)                    conv1 dgrad, conv1 wgrad
+
+    (a stride-2 conv1 has no "f" image, hence no f cell: the tail below it raises nothing and its weight gradient stays fp32.)
+
+    UNLIKE the ST-GCN plan above, a cell here exists whenever its image exists, whatever SAR_SPLIT_KINDS_PATHB and the arithmetic say,
+    and its producer raises it even when no launch reads it -- under a kinds subset, under bf16x6, and where the wrapper demotes
+    every reader.  That is what the engine has always launched, and it is why the f cell is raised whenever it exists: the forward
+    launch AND the weight gradient read it (with SAR_SPLIT_KINDS_PATHB=dgrad,wgrad the weight gradient once read a bound that only a
+    split forward launch used to raise).  The "no unread cell" rule would change the arguments of the producer launches."""
+
+    def __init__(self, eng, kinds):
+        self.convs, self.blocks = eng.convs, eng.blocks
+        self.packed, self.cells, self.bounds = None, None, []
+        self.recs = {name: ConvPlan() for name in eng.convs}
+        if not eng.split:
+            return
+        self.packed = sp = ops.PackedSplitWeights(eng.split)
+        for name, cv in eng.convs.items():
+            src, cc = eng.offsets[name + ".weight"], cv.cin * cv.cout
+            for v in _views(cv):
+                if v == "f":
+                    sp.add((name, v), src, cc, cv.cout, 1, 9, cv.cin, cv.cout)
+                elif cv.stride == 1:      # mirrored taps (include/sar_hip.h sar_conv2d_gemm_split)
+                    sp.add((name, v), src + 8 * cc, -cc, 1, cv.cout, 9, cv.cout, cv.cin)
+                else:                     # the stride-2 data gradient addresses the forward taps of the (tap, m, c) view
+                    sp.add((name, v), src, cc, 1, cv.cout, 9, cv.cout, cv.cin)
+        sp.finalize(eng.device)
+        self.cells = torch.zeros(max(1, len(sp.items)), dtype=torch.int32, device=eng.device)      # one per image, in its order
+        for name, cv in eng.convs.items():
+            rec = self.recs[name]
+            for v in _views(cv):
+                setattr(rec, v, self.cells[sp.item_of[(name, v)]:][:1])
+            gemm = lambda v: dict(split=eng.split, packed=sp.image((name, v)), bounds=(getattr(rec, v), sp.bound((name, v))))
+            if rec.f is not None and "fwd" in kinds:
+                rec.fwd = gemm("f")
+            if rec.b is not None and "dgrad" in kinds:
+                rec.dgrad = gemm("b")
+            if rec.f is not None and "wgrad" in kinds:
+                rec.wgrad = dict(split=eng.split, bounds=(rec.f, rec.b))
+        # the producers that are not a convolution's own backward passes: Samuelson bounds and block tails
+        self._samuelson(eng, "bn1", eng.blocks[0][0] + "conv1", "conv1")
+        for i, blk in enumerate(eng.blocks):
+            self._samuelson(eng, blk[0] + "bn1", blk[0] + "conv2", blk[0] + "conv1")
+            if i + 1 < len(eng.blocks):
+                self.recs[blk[0] + "conv2"].y = self.recs[eng.blocks[i + 1][0] + "conv1"].f
+
+    def _samuelson(self, eng, bn, consumer, producer):
+        rec = self.recs[consumer]
+        if rec.f is not None:
+            rec.bound = len(self.bounds)
+            self.bounds.append((eng.p[bn + ".weight"], eng.p[bn + ".bias"], rec.f, producer))
+
+    def rec(self, name, training=True):
+        """the record of convolution `name` in a training step; inference keeps the fp32 kernels and raises nothing"""
+        return self.recs[name] if training else CONV_OFF
+
+    begin_step = SplitPlan.begin_step      # (reads .packed and .cells only)
+
+    def raise_bn_bound(self, i, count):
+        """entry i of bounds (None: nothing) from its gamma / beta and the sample count"""
+        if i is not None:
+            gamma, beta, cell, _ = self.bounds[i]
+            ops.bn_bound(gamma, beta, count, cell)
+
+    def raise_bn_bounds(self, B, H, W):
+        """every Samuelson cell of a step on B images of H x W, from the geometry alone: what forward() raises layer by layer when
+        the bounds are not forked"""
+        def osz(n, cv):
+            return (n + 2 * cv.pad - cv.k) // cv.stride + 1
+        cv = self.convs["conv1"]
+        H, W = osz(H, cv), osz(W, cv)
+        count = {"conv1": B * H * W}
+        H, W = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1      # the stem's max-pool
+        for blk in self.blocks:
+            cv = self.convs[blk[0] + "conv1"]
+            H, W = osz(H, cv), osz(W, cv)
+            count[cv.name] = B * H * W
+        for i, (_, _, _, producer) in enumerate(self.bounds):
+            self.raise_bn_bound(i, count[producer])

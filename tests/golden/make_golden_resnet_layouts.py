@@ -3,7 +3,9 @@
 streams / images exist).  Run at the commit whose layout is the reference -- the fixture pins it for every later restructuring of the
 constructor, so it is never regenerated from the code under test (tests/test_resnet_layout.py imports configs() and layout() from
 here).  The reference commit's constructor entered torch.cuda.device() whatever the device: build() replaces it by a null context
-while it constructs (harmless where the constructor no longer does)."""
+while it constructs (harmless where the constructor no longer does).  One recorded value was changed by hand since: a CPU engine in a
+split arithmetic now builds its term images and its plan like a device one (sar_amd/split_plan.py ResNetPlan; the schedule of
+tests/test_pathb_schedule.py is replayed on it), so "spacked" is None of the two fp32 configurations only."""
 import contextlib
 import hashlib
 import json

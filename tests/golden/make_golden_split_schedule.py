@@ -172,8 +172,8 @@ def first_difference(got, want):
     return next((k for k in range(n) if got[3 * k:3 * k + 3] != want[3 * k:3 * k + 3]), n)
 
 
-def check_invariants(tr):
-    """every cell an fp16 split launch reads was raised earlier in the step; no raised cell goes unread.  Returns a list of complaints."""
+def unraised_reads(tr):
+    """every cell an fp16 split launch reads was raised earlier in the step.  Returns (a list of complaints, the cells raised, read)."""
     raised, read, bad = set(), set(), []
     for n, ev in enumerate(tr):
         if "raise" in ev:
@@ -191,8 +191,13 @@ def check_invariants(tr):
                 read.add(c)
                 if c not in raised:
                     bad.append("launch %d (%s) reads cell %s, which nothing raised before it" % (n, ev, c))
-    bad += ["cell %s is raised and never read" % c for c in sorted(raised - read)]
-    return bad
+    return bad, raised, read
+
+
+def check_invariants(tr):
+    """unraised_reads(), and no raised cell goes unread.  Returns a list of complaints."""
+    bad, raised, read = unraised_reads(tr)
+    return bad + ["cell %s is raised and never read" % c for c in sorted(raised - read)]
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """The constructor of Path B's classifier lays out what tests/golden/resnet_layouts.json recorded (written once by
 tests/golden/make_golden_resnet_layouts.py, before the engine moved onto sar_amd/engine.py): parameter names, shapes and offsets in
 order, flat size, gradient buckets in hand-over order, BatchNorm names, the data-gradient re-layout, the bytes of the initial
-parameters, and which streams / images a CPU engine has.  CPU only."""
+parameters, and which streams / images a CPU engine has (no streams; term images exactly in a split arithmetic).  CPU only."""
 import json
 import os
 import sys
