@@ -231,10 +231,10 @@ def split_applicable(mode, V, Kc, M, taps, stride, tables=None, pro=None, transp
     return mode == L.SAR_CONV_TEMPORAL and taps == 9 and V == 25 and 8 <= Kc <= 256 and M % 8 == 0 and stride in (1, 2)
 
 
-def _pack_split_single(W, w_stride_tap, w_stride_c, taps, Kc, M, arith):
+def _pack_split_single(W, w_stride_tap, w_stride_c, taps, Kc, M, arith, src_off=0):
     """one tensor, packed on the spot (kernel tests / probes; the engines keep a PackedSplitWeights): (image, w_bound)"""
     pk = PackedSplitWeights(arith)
-    pk.add("w", 0, w_stride_tap, w_stride_c, 1, taps, Kc, M)
+    pk.add("w", src_off, w_stride_tap, w_stride_c, 1, taps, Kc, M)
     pk.finalize(W.device)
     pk.refresh(W)
     return pk.image("w"), pk.bound("w")
@@ -250,96 +250,174 @@ def _src_bound_single(src, pro):
     return cells[1:2]
 
 
-def conv_gemm(mode, src, out, W, w_stride_tap, w_stride_c, *, B, V, T_src, T_out, Kc, M, taps, stride=1, pad=0,
-              transposed=False, bias=None, pro=None, pro_relu=False, tables=None, epi=L.SAR_EPI_NONE, aux=None,
-              aux_affine=None, aux_mean=None, bf16=False, packed=None, partials_out=None, aux2=None, aux_mask=None,
-              split="default", bounds=None, aux_even_frames=False):
-    """Launch sar_conv_gemm_f32 -- or, with bf16=True, sar_conv_gemm_bf16 (M % 8 == 0, Kc >= 16: bf16
-    MFMA operands, fp32 everything else; other shapes stay on the fp32 kernel); or, with split="bf16x6", the fp32-accurate
-    split arithmetic on the bf16 / fp16 matrix pipe (sar_conv_gemm_split; `packed` = the PackedSplitWeights image or None = pack
-    here; bounds = (src_bound, w_bound) cells for the fp16 arithmetics, None = computed here by device kernels).  Returns
-    (partials, nparts) when the epilogue reduces, else None."""
-    lib = L.load()
+def conv_gemm_route(split, bf16, mode, V, Kc, M, taps, stride, tables=None, pro=None, transposed=False, pad=0, epi=L.SAR_EPI_NONE):
+    """the kernel of a conv_gemm call: a split arithmetic (sar_conv_gemm_split), "bf16" (sar_conv_gemm_bf16) or None (sar_conv_gemm_f32).
+    `split` ("default" = DEFAULT_SPLIT) is kept on the shapes of split_applicable() -- the gated epilogue on the graph kernel only, the
+    graph and 1-tap kernels in bf16x6 / f16x3a only -- and wins over bf16.  No library, no tensor (tables: g_flags, n_dense_lists)."""
     if split == "default":
         split = DEFAULT_SPLIT
-    split = split if (split and split_applicable(mode, V, Kc, M, taps, stride, tables, pro, transposed, pad)
-                      and (epi != L.SAR_EPI_ADD_GATE or mode == L.SAR_CONV_GRAPH)) else None
-    if split and (mode == L.SAR_CONV_GRAPH or taps == 1) and split not in ("bf16x6", "f16x3a"):
-        split = None
-    if split:
-        bf16 = False
-    d = ConvDesc()
-    d.mode, d.transposed, d.B, d.V = mode, int(transposed), B, V
-    d.T_src, d.T_out, d.Kc, d.M = T_src, T_out, Kc, M
-    d.taps, d.stride, d.pad, d.pro_relu, d.epi = taps, stride, pad, int(pro_relu), epi
-    _f32(src), _f32(out), _f32(W)
-    d.src, d.ld_src = ptr(src), src.stride(0)
-    d.out, d.ld_out = ptr(out), out.stride(0)
-    bf16 = bf16 and M % 8 == 0 and Kc >= 16
-    use_packed = (bf16 or split) and packed is not None      # packed: the operand image from PackedWeights (W is then not read)
-    w_bound = bounds[1] if bounds is not None else None
-    if split and packed is None:
-        packed, w_bound = _pack_split_single(W, w_stride_tap, w_stride_c, taps, Kc, M, split)
-        use_packed = True
-    d.W, d.w_stride_tap, d.w_stride_c = (None if use_packed else ptr(W)), w_stride_tap, w_stride_c
-    d.bias = ptr(_f32(bias))
+    if (split and split_applicable(mode, V, Kc, M, taps, stride, tables, pro, transposed, pad)
+            and (epi != L.SAR_EPI_ADD_GATE or mode == L.SAR_CONV_GRAPH)
+            and (split in ("bf16x6", "f16x3a") or not (mode == L.SAR_CONV_GRAPH or taps == 1))):
+        return split
+    return "bf16" if (bf16 and M % 8 == 0 and Kc >= 16) else None
+
+
+# ---- what the launch wrappers below (and the CN8 pair of sar_amd/ops8.py) share: DESIGN.md, "The convolution launch layer"
+_CN = (lambda t: (ptr(_f32(t)), t.stride(0)), _f32)      # an fp32 CN operand -> (pointer, leading dimension); a per-channel vector
+_REDUCING = (L.SAR_EPI_STATS, L.SAR_EPI_MASK, L.SAR_EPI_ADD_GATE)
+
+
+def _fold_and_gather(d, vec, pro, tables, g_flags):
+    """the folded prologue's affine and the gather tables of a ConvDesc / WgradDesc"""
     if pro is not None:
-        d.pro_scale, d.pro_shift = ptr(_f32(pro[0])), ptr(_f32(pro[1]))
+        d.pro_scale, d.pro_shift = ptr(vec(pro[0])), ptr(vec(pro[1]))
     if tables is not None:
         d.g_idx, d.g_wt, d.g_colsum = ptr(tables.idx), ptr(tables.wt), ptr(tables.colsum)
         for i in range(3):
             d.nz[i] = tables.nz[i]
-        # aux_even_frames: `aux` holds the even output frames only (include/sar_hip.h SAR_GRAPH_AUX_EVEN_FRAMES: the skip gradient through a
-        # stride-2 residual convolution, computed compactly)
-        d.g_flags = (tables.g_flags | (L.SAR_GRAPH_ONE_TILE_WG if GRAPH_ONE_TILE_WG else 0)
-                     | (L.SAR_GRAPH_AUX_EVEN_FRAMES if aux_even_frames else 0))
+        d.g_flags = g_flags
+
+
+def _conv_desc(fmt, mode, src, out, B, V, T_src, T_out, Kc, M, taps, stride=1, pad=0, transposed=False, epi=L.SAR_EPI_NONE, pro=None,
+               pro_relu=False, tables=None, g_flags=0, bias=None, aux=None, aux_affine=None, aux_mean=None):
+    """the ConvDesc of a launch, but for its weights, second auxiliary and partials.  fmt = (operand, vec) reads the storage format:
+    operand(t) -> (checked pointer, leading dimension), vec(t) -> a checked per-channel fp32 vector; src / out None: geometry only"""
+    operand, vec = fmt
+    d = ConvDesc()
+    d.mode, d.transposed, d.B, d.V = mode, int(transposed), B, V
+    d.T_src, d.T_out, d.Kc, d.M = T_src, T_out, Kc, M
+    d.taps, d.stride, d.pad, d.pro_relu, d.epi = taps, stride, pad, int(pro_relu), epi
+    if src is not None:
+        d.src, d.ld_src = operand(src)
+        d.out, d.ld_out = operand(out)
+    d.bias = ptr(vec(bias))
+    _fold_and_gather(d, vec, pro, tables, g_flags)
     if aux is not None:
-        d.aux, d.ld_aux = ptr(_f32(aux)), aux.stride(0)
+        d.aux, d.ld_aux = operand(aux)
     if aux_affine is not None:
-        d.aux_scale, d.aux_shift = ptr(_f32(aux_affine[0])), ptr(_f32(aux_affine[1]))
-    d.aux_mean = ptr(_f32(aux_mean))
+        d.aux_scale, d.aux_shift = ptr(vec(aux_affine[0])), ptr(vec(aux_affine[1]))
+    d.aux_mean = ptr(vec(aux_mean))
+    return d
+
+
+def _wgrad_desc(fmt, mode, src, dout, B, V, T_src, T_out, Kc, M, taps, stride, pad, pro, pro_relu, tables, g_flags,
+                w_stride_tap, w_stride_c, wsize, bsize):
+    """the WgradDesc of a launch, but for nsplit and the slab; fmt as in _conv_desc"""
+    operand, vec = fmt
+    d = WgradDesc()
+    d.mode, d.B, d.V, d.T_src, d.T_out, d.Kc, d.M = mode, B, V, T_src, T_out, Kc, M
+    d.taps, d.stride, d.pad, d.pro_relu = taps, stride, pad, int(pro_relu)
+    d.src, d.ld_src = operand(src)
+    d.dout, d.ld_dout = operand(dout)
+    _fold_and_gather(d, vec, pro, tables, g_flags)
+    d.w_stride_tap, d.w_stride_c, d.wsize, d.bsize = w_stride_tap, w_stride_c, wsize, bsize
+    return d
+
+
+def _reducing_partials(d, nparts, what, M, device, partials_out=None):
+    """d.partials = the (M, nparts, 2) partial sums of a reducing epilogue, returned.  nparts: the answer of the route's `nparts` query,
+    raised under the name `what` when it is no count; partials_out: caller-owned rows of a stacked partials tensor (sar_amd/stgin.py)"""
+    if nparts <= 0:
+        check(nparts or -1, what)
+    if partials_out is None:
+        partials_out = torch.empty((M, nparts, 2), dtype=torch.float32, device=device)
+    assert partials_out.shape == (M, nparts, 2) and partials_out.is_contiguous()
+    d.partials = ptr(partials_out)
+    return partials_out
+
+
+def _wgrad_slab(d, slabs, out, nsplit, n, device):
+    """d.nsplit, d.slab and the (nsplit, n) slab of the weight gradient that ends in out[0:n]: the batch's (a SlabBatch) or its own"""
+    assert out.numel() >= n and out.is_contiguous()
+    slab = slabs.slab(out, nsplit, n) if slabs is not None else torch.empty((nsplit, n), dtype=torch.float32, device=device)
+    d.nsplit, d.slab = nsplit, ptr(slab)
+    return slab
+
+
+def _wgrad_slab_done(slabs, slab, nsplit, n, out):
+    """behind the weight-gradient launch: the slabs are summed by the batch's next flush(), or by a launch of their own"""
+    if slabs is not None:
+        return slabs.add(slab, nsplit, n, out)
+    check(L.load().sar_slab_reduce_f32(ptr(slab), nsplit, n, n, ptr(out), stream_ptr()), "sar_slab_reduce_f32")
+
+
+def _split_inputs(split, bounds, sources, packed=None, pack=None):
+    """([bound cell, bound cell], operand image) of a split launch.  The engines hand in all of it (sar_amd/split_plan.py); a stand-alone
+    call (kernel tests, probes) leaves None what device kernels make here: first the image and the second cell = its weight bound by
+    pack() -> (image, w_bound), then, for the fp16 arithmetics, the missing cell of every (tensor, folded affine) of `sources`"""
+    cells = list(bounds) if bounds is not None else [None, None]
+    if pack is not None and packed is None:
+        packed, cells[1] = pack()
+    if split.startswith("f16"):
+        for i, (t, pro) in enumerate(sources):
+            if cells[i] is None:
+                cells[i] = _src_bound_single(t, pro)
+    return cells, packed
+
+
+def conv_gemm(mode, src, out, W, w_stride_tap, w_stride_c, *, B, V, T_src, T_out, Kc, M, taps, stride=1, pad=0,
+              transposed=False, bias=None, pro=None, pro_relu=False, tables=None, epi=L.SAR_EPI_NONE, aux=None,
+              aux_affine=None, aux_mean=None, bf16=False, packed=None, partials_out=None, aux2=None, aux_mask=None,
+              split="default", bounds=None, aux_even_frames=False):
+    """Launch sar_conv_gemm_f32 -- or, with bf16=True, sar_conv_gemm_bf16 (M % 8 == 0, Kc >= 16: bf16 MFMA operands, fp32 everything
+    else; other shapes stay on the fp32 kernel); or, with split="bf16x6", the fp32-accurate split arithmetic on the bf16 / fp16 matrix
+    pipe (sar_conv_gemm_split; `packed` = the PackedSplitWeights image or None = pack here; bounds = (src_bound, w_bound) cells for the
+    fp16 arithmetics, None = computed here by device kernels).  Returns (partials, nparts) when the epilogue reduces, else None."""
+    lib = L.load()
+    route = conv_gemm_route(split, bf16, mode, V, Kc, M, taps, stride, tables, pro, transposed, pad, epi)
+    bf16 = route == "bf16"
+    split = None if bf16 else route
+    # aux_even_frames: `aux` holds the even output frames only (include/sar_hip.h SAR_GRAPH_AUX_EVEN_FRAMES: the skip gradient through a
+    # stride-2 residual convolution, computed compactly)
+    g_flags = 0 if tables is None else (tables.g_flags | (L.SAR_GRAPH_ONE_TILE_WG if GRAPH_ONE_TILE_WG else 0)
+                                        | (L.SAR_GRAPH_AUX_EVEN_FRAMES if aux_even_frames else 0))
+    d = _conv_desc(_CN, mode, src, out, B, V, T_src, T_out, Kc, M, taps, stride, pad, transposed, epi, pro, pro_relu, tables, g_flags,
+                   bias, aux, aux_affine, aux_mean)
+    _f32(W)
+    use_packed = split or (bf16 and packed is not None)      # packed: the operand image from PackedWeights (W is then not read)
+    d.W, d.w_stride_tap, d.w_stride_c = (None if use_packed else ptr(W)), w_stride_tap, w_stride_c
     if epi == L.SAR_EPI_ADD_GATE:      # fp32 kernel only: aux2 [M][ld] floats, aux_mask [M][ld / 4] bytes (relu_mask layout)
         assert not bf16 and aux2 is not None and aux_mask is not None and aux_mask.dtype == torch.uint8
         assert aux2.stride(0) % 4 == 0 and aux_mask.shape == (M, aux2.stride(0) // 4) and aux_mask.is_contiguous()
         d.aux2, d.ld_aux2, d.aux_mask = ptr(_f32(aux2)), aux2.stride(0), ptr(aux_mask)
-    partials = None
-    nparts = 0
-    if epi in (L.SAR_EPI_STATS, L.SAR_EPI_MASK, L.SAR_EPI_ADD_GATE):
+    partials, nparts = None, 0
+    if epi in _REDUCING:
         nparts = lib.sar_conv_gemm_split_nparts(C.byref(d)) if split else lib.sar_conv_gemm_nparts(C.byref(d))
-        if nparts <= 0:
-            check(nparts or -1, "sar_conv_gemm_nparts")
-        if partials_out is not None:      # caller-owned rows of a stacked partials tensor (sar_amd/stgin.py)
-            assert partials_out.shape == (M, nparts, 2) and partials_out.is_contiguous()
-            partials = partials_out
-        else:
-            partials = torch.empty((M, nparts, 2), dtype=torch.float32, device=src.device)
-        d.partials = ptr(partials)
+        partials = _reducing_partials(d, nparts, "sar_conv_gemm_nparts", M, src.device, partials_out)
     # algorithmic work: the forward conv's MACs (a data gradient costs the same MACs as its forward conv)
     n_conv = B * (T_src if transposed else T_out) * V
-    flops = 2.0 * M * Kc * taps * n_conv
+    flops, nbytes = 2.0 * M * Kc * taps * n_conv, 4.0 * (Kc * B * T_src * V + M * B * T_out * V)
     tag = ("gemm_graph" if mode == L.SAR_CONV_GRAPH else ("gemm_temporal%d%s" % (taps, "_dgrad" if transposed else "")))
     if split:
-        src_bound = bounds[0] if bounds is not None else None
-        if split.startswith("f16") and src_bound is None:
-            src_bound = _src_bound_single(src, pro)
-        with profiler.region(tag + "_split", flops, 4.0 * (Kc * B * T_src * V + M * B * T_out * V)):
+        (src_bound, w_bound), packed = _split_inputs(split, bounds, ((src, pro),), packed,
+                                                     lambda: _pack_split_single(W, w_stride_tap, w_stride_c, taps, Kc, M, split))
+        with profiler.region(tag + "_split", flops, nbytes):
             check(lib.sar_conv_gemm_split(C.byref(d), L.SAR_SPLIT[split], ptr(packed), ptr(src_bound), ptr(w_bound), stream_ptr()),
                   "sar_conv_gemm_split")
     elif bf16:
         ws = packed if use_packed else torch.empty(lib.sar_conv_gemm_bf16_workspace_bytes(C.byref(d)), dtype=torch.uint8,
                                                    device=src.device)
-        with profiler.region(tag + "_bf16", flops, 4.0 * (Kc * B * T_src * V + M * B * T_out * V)):
+        with profiler.region(tag + "_bf16", flops, nbytes):
             check(lib.sar_conv_gemm_bf16(C.byref(d), ptr(ws), stream_ptr()), "sar_conv_gemm_bf16")
     else:
-        with profiler.region(tag, flops, 4.0 * (Kc * B * T_src * V + M * B * T_out * V)):
+        with profiler.region(tag, flops, nbytes):
             check(lib.sar_conv_gemm_f32(C.byref(d), stream_ptr()), "sar_conv_gemm_f32")
     return (partials, nparts) if partials is not None else None
+
+
+def conv_gemm_nparts(B, V, T_src, T_out, Kc, M, taps=1, stride=1, pad=0, transposed=False, epi=L.SAR_EPI_STATS):
+    """partial sums per output row that sar_conv_gemm_f32 (TEMPORAL) writes for this geometry"""
+    d = _conv_desc(_CN, L.SAR_CONV_TEMPORAL, None, None, B, V, T_src, T_out, Kc, M, taps, stride, pad, transposed, epi)
+    n = L.load().sar_conv_gemm_nparts(C.byref(d))
+    if n <= 0:
+        check(n or -1, "sar_conv_gemm_nparts")
+    return n
 
 
 _WGRAD1_SLOTS = int(os.environ.get("SAR_WGRAD1_SLOTS", "1024"))      # workgroups in flight of the 1-tap weight gradients
 _WGRAD9_SLOTS = int(os.environ.get("SAR_WGRAD9_SLOTS", "1024"))      # ... of the 9-tap temporal ones (sweep knobs)
 _WGRADG_SLOTS = int(os.environ.get("SAR_WGRADG_SLOTS", "512"))       # ... of the graph ones
-
 
 # columns per workgroup of the first layer's streaming weight gradient (graph_wgrad_small4_kernel: 256-column iterations)
 _WGRAD_SMALL_COLS = int(os.environ.get("SAR_WGRAD_SMALL_COLS", "4096"))
@@ -394,93 +472,86 @@ class SlabBatch:
         check(L.load().sar_slab_reduce_batch_f32(ptr(ent[0]), len(key), ent[1], stream_ptr()), "sar_slab_reduce_batch_f32")
 
 
+def conv_wgrad_route(split, bf16, mode, V, taps, stride, pad, blocks):
+    """(kernel, sp) of a conv_wgrad call: a split arithmetic (sar_conv_wgrad_split: bf16x6 / f16x3a where blocks(arith) -> sp =
+    (workgroups, wk, kt), the answer of sar_conv_wgrad_split_blocks for the call's geometry, counts workgroups), "bf16"
+    (sar_conv_wgrad_bf16) or None (sar_conv_wgrad_f32).  `split`: "default" = DEFAULT_SPLIT."""
+    if split == "default":
+        split = DEFAULT_SPLIT
+    if split in ("bf16x6", "f16x3a") and not (taps == 1 and mode == L.SAR_CONV_TEMPORAL and not TAP1_SPLIT):
+        sp = blocks(split)
+        if sp[0] > 0:
+            return split, sp
+    # (a bf16 graph weight gradient was built and measured: with the adjacency gather in its stager it ran 1.7x SLOWER
+    # than the fp32 kernel -- 9.0 vs 5.4 ms per step -- so the graph weight gradient stays on the fp32 kernel)
+    if bf16 and mode == L.SAR_CONV_TEMPORAL and taps == 9 and V == 25 and (stride == 1 or (stride == 2 and pad == 3)):
+        return "bf16", None
+    return None, None
+
+
+def conv_wgrad_nsplit(route, sp, nsplit, mode, B, V, T_out, Kc, M, taps, stride, pro=None):
+    """the slabs of a conv_wgrad launch: the caller's `nsplit` (rounded up to the split kernel's multiple) or the default of the kernel
+    that runs; (route, sp) as conv_wgrad_route returns them"""
+    if route not in (None, "bf16"):
+        sp_blocks, wk, kt = sp
+        if nsplit is None:      # one round of the 512 resident workgroups (two per CU); SAR_WGRAD_SPLIT_SLOTS: experiment
+            ntiles = B * ((T_out * V + kt - 1) // kt)
+            return max(1, min(ntiles, _WGRADS_SLOTS // sp_blocks)) * wk
+        return (nsplit + wk - 1) // wk * wk
+    if nsplit is not None:
+        return nsplit
+    if route == "bf16":     # 64 (m) x 64 / 32 (c, stride 1 / 2) weight blocks, 8-frame tiles; one round of the 512 resident workgroups
+        ntiles = B * ((T_out + 7) // 8)
+        cb = 64 if stride == 1 else 32
+        return max(1, min(ntiles, 512 // (((M + 63) // 64) * ((Kc + cb - 1) // cb))))
+    if mode == L.SAR_CONV_GRAPH and Kc <= 4 and pro is None:
+        # streaming kernel of the 3-channel first layer (conv_wgrad.hip: graph_wgrad_small_kernel): ~8 chunks of 64 columns per
+        # workgroup (its loop is latency-bound: many short workgroups, not few long ones)
+        return max(1, min(4096, (B * T_out * V + _WGRAD_SMALL_COLS - 1) // _WGRAD_SMALL_COLS))
+    ct = 32 if (mode == L.SAR_CONV_TEMPORAL and taps == 9) else 64
+    ft, bf = max(2, min((128 // V) & ~1, (T_out + 1) & ~1)), 64
+    if mode == L.SAR_CONV_GRAPH and V == 25 and Kc >= 32 and pro is None:      # fixed-geometry kernel: 2-frame tiles, 128 x 64 blocks when M > 64
+        ft, bf = 2, (128 if M > 64 else 64)
+    ntiles = B * ((T_out + ft - 1) // ft)
+    wgs = ((M + bf - 1) // bf) * ((Kc + ct - 1) // ct)
+    # workgroups in flight: two rounds of the 512 resident slots for the temporal kernels, one for the graph kernel
+    # (tools/nsplit_sweep.py)
+    target = _WGRADG_SLOTS if (mode == L.SAR_CONV_GRAPH and ft == 2) else (_WGRAD1_SLOTS if taps == 1 else _WGRAD9_SLOTS)
+    return max(1, min(ntiles, (target + wgs - 1) // wgs))
+
+
 def conv_wgrad(mode, src, dout, dW_out, *, B, V, T_src, T_out, Kc, M, taps, stride=1, pad=0, pro=None, pro_relu=False,
                tables=None, w_stride_tap, w_stride_c, wsize, bsize, nsplit=None, bf16=False, split="default", bounds=None,
                slabs=None):
     """dW (and dbias, stored right behind it) -> dW_out[0 : wsize+bsize] (flat float32 view).  bf16=True routes the
     9-tap temporal operator (V = 25; stride 1, or stride 2 with the even-T SAME padding 3) to sar_conv_wgrad_bf16 (bf16 MFMA operands, fp32 accumulation and bias
-    sums); every other shape stays on the fp32 kernel."""
+    sums); every other shape stays on the fp32 kernel.  split="bf16x6" / "f16x3a": the split arithmetic of csrc/conv_wgrad_split.hip
+    where it is built (bounds = (src_bound, dout_bound) cells for the fp16 arithmetic, None = computed here by device kernels); other
+    shapes stay on the fp32 kernel.  slabs (SlabBatch): the slabs are summed by the batch's next flush() instead of by a launch of
+    their own."""
     lib = L.load()
-    d = WgradDesc()
-    d.mode, d.B, d.V, d.T_src, d.T_out, d.Kc, d.M = mode, B, V, T_src, T_out, Kc, M
-    d.taps, d.stride, d.pad, d.pro_relu = taps, stride, pad, int(pro_relu)
-    _f32(src), _f32(dout)
-    d.src, d.ld_src, d.dout, d.ld_dout = ptr(src), src.stride(0), ptr(dout), dout.stride(0)
-    if pro is not None:
-        d.pro_scale, d.pro_shift = ptr(_f32(pro[0])), ptr(_f32(pro[1]))
-    if tables is not None:
-        d.g_idx, d.g_wt, d.g_colsum = ptr(tables.idx), ptr(tables.wt), ptr(tables.colsum)
-        for i in range(3):
-            d.nz[i] = tables.nz[i]
-        d.g_flags = tables.g_flags
-    # split="bf16x6" / "f16x3a": the split arithmetic of csrc/conv_wgrad_split.hip where it is built (bounds = (src_bound,
-    # dout_bound) cells for the fp16 arithmetic, None = computed here by device kernels); other shapes stay on the fp32 kernel
-    if split == "default":
-        split = DEFAULT_SPLIT
-    if taps == 1 and mode == L.SAR_CONV_TEMPORAL and not TAP1_SPLIT:
-        split = None
-    sp_blocks = 0
-    if split in ("bf16x6", "f16x3a"):
+    d = _wgrad_desc(_CN, mode, src, dout, B, V, T_src, T_out, Kc, M, taps, stride, pad, pro, pro_relu, tables,
+                    tables.g_flags if tables is not None else 0, w_stride_tap, w_stride_c, wsize, bsize)
+    def blocks(arith):      # (what the route asks the library)
         wk, kt = C.c_int(0), C.c_int(0)
-        sp_blocks = lib.sar_conv_wgrad_split_blocks(C.byref(d), L.SAR_SPLIT[split], C.byref(wk), C.byref(kt))
-        if sp_blocks > 0:
-            bf16 = False
-            if nsplit is None:      # one round of the 512 resident workgroups (two per CU); SAR_WGRAD_SPLIT_SLOTS: experiment
-                ntiles = B * ((T_out * V + kt.value - 1) // kt.value)
-                nsplit = max(1, min(ntiles, _WGRADS_SLOTS // sp_blocks)) * wk.value
-            else:
-                nsplit = (nsplit + wk.value - 1) // wk.value * wk.value
-    split = split if sp_blocks > 0 else None
-    ct = 32 if (mode == L.SAR_CONV_TEMPORAL and taps == 9) else 64
-    # (a bf16 graph weight gradient was built and measured: with the adjacency gather in its stager it ran 1.7x SLOWER
-    # than the fp32 kernel -- 9.0 vs 5.4 ms per step -- so the graph weight gradient stays on the fp32 kernel)
-    bf16 = bf16 and mode == L.SAR_CONV_TEMPORAL and taps == 9 and V == 25 and (stride == 1 or (stride == 2 and pad == 3))
-    if bf16 and nsplit is None:     # 64 (m) x 64 / 32 (c, stride 1 / 2) weight blocks, 8-frame tiles; one round of the 512 resident workgroups
-        ntiles = B * ((T_out + 7) // 8)
-        cb = 64 if stride == 1 else 32
-        nsplit = max(1, min(ntiles, 512 // (((M + 63) // 64) * ((Kc + cb - 1) // cb))))
-    if nsplit is None and mode == L.SAR_CONV_GRAPH and Kc <= 4 and pro is None:
-        # streaming kernel of the 3-channel first layer (conv_wgrad.hip: graph_wgrad_small_kernel): ~8 chunks of 64 columns per
-        # workgroup (its loop is latency-bound: many short workgroups, not few long ones)
-        nsplit = max(1, min(4096, (B * T_out * V + _WGRAD_SMALL_COLS - 1) // _WGRAD_SMALL_COLS))
-    if nsplit is None:
-        ft = max(2, min((128 // V) & ~1, (T_out + 1) & ~1))
-        bf = 64
-        if mode == L.SAR_CONV_GRAPH and V == 25 and Kc >= 32 and pro is None:      # fixed-geometry kernel: 2-frame tiles, 128 x 64 blocks when M > 64
-            ft, bf = 2, (128 if M > 64 else 64)
-        ntiles = B * ((T_out + ft - 1) // ft)
-        wgs = ((M + bf - 1) // bf) * ((Kc + ct - 1) // ct)
-        # workgroups in flight: two rounds of the 512 resident slots for the temporal kernels, one for the graph kernel
-        # (tools/nsplit_sweep.py)
-        target = _WGRADG_SLOTS if (mode == L.SAR_CONV_GRAPH and ft == 2) else (_WGRAD1_SLOTS if taps == 1 else _WGRAD9_SLOTS)
-        nsplit = max(1, min(ntiles, (target + wgs - 1) // wgs))
-    d.nsplit = nsplit
-    d.w_stride_tap, d.w_stride_c, d.wsize, d.bsize = w_stride_tap, w_stride_c, wsize, bsize
-    assert dW_out.numel() >= wsize + bsize and dW_out.is_contiguous()
-    # slabs (SlabBatch): the slabs are summed by the batch's next flush() instead of by a launch of their own
-    slab = (slabs.slab(dW_out, nsplit, wsize + bsize) if slabs is not None
-            else torch.empty((nsplit, wsize + bsize), dtype=torch.float32, device=src.device))
-    d.slab = ptr(slab)
+        return lib.sar_conv_wgrad_split_blocks(C.byref(d), L.SAR_SPLIT[arith], C.byref(wk), C.byref(kt)), wk.value, kt.value
+    route, sp = conv_wgrad_route(split, bf16, mode, V, taps, stride, pad, blocks)
+    nsplit, n = conv_wgrad_nsplit(route, sp, nsplit, mode, B, V, T_out, Kc, M, taps, stride, pro), wsize + bsize
+    slab = _wgrad_slab(d, slabs, dW_out, nsplit, n, src.device)
     tag = "wgrad_graph" if mode == L.SAR_CONV_GRAPH else "wgrad_temporal%d" % taps
-    if split:
-        src_bound, dout_bound = bounds if bounds is not None else (None, None)
-        if split.startswith("f16") and bounds is None:
-            src_bound = _src_bound_single(src, pro)
-            dout_bound = _src_bound_single(dout, None)
-    with profiler.region(tag + ("_split" if split else "_bf16" if bf16 else ""), 2.0 * M * Kc * taps * B * T_out * V,
-                         4.0 * (Kc * B * T_src * V + M * B * T_out * V)):
+    flops, nbytes = 2.0 * M * Kc * taps * B * T_out * V, 4.0 * (Kc * B * T_src * V + M * B * T_out * V)
+    split = route if route != "bf16" else None
+    if split:      # (cells handed in are taken as they are; with none, both are made here)
+        (src_bound, dout_bound), _ = _split_inputs(split, bounds, ((src, pro), (dout, None)) if bounds is None else ())
+    with profiler.region(tag + ("_split" if split else "_bf16" if route else ""), flops, nbytes):
         if split:
             check(lib.sar_conv_wgrad_split(C.byref(d), L.SAR_SPLIT[split], ptr(src_bound), ptr(dout_bound), stream_ptr()),
                   "sar_conv_wgrad_split")
-        elif bf16:
+        elif route:
             check(lib.sar_conv_wgrad_bf16(C.byref(d), stream_ptr()), "sar_conv_wgrad_bf16")
         else:
             check(lib.sar_conv_wgrad_f32(C.byref(d), stream_ptr()), "sar_conv_wgrad_f32")
-    if slabs is not None:
-        slabs.add(slab, nsplit, wsize + bsize, dW_out)
-        return
-    check(lib.sar_slab_reduce_f32(ptr(slab), nsplit, wsize + bsize, wsize + bsize, ptr(dW_out), stream_ptr()),
-          "sar_slab_reduce_f32")
+    _wgrad_slab_done(slabs, slab, nsplit, n, dW_out)
 
 
 def bn_finalize(partials, nparts, C_, count, eps, momentum, unbiased_running, gamma, beta, running_mean, running_var,
@@ -841,7 +912,6 @@ def gin_sample_eps_grad(x, dout, deps, F, V, N, scratch=None):
                                           stream_ptr()), "sar_gin_sample_eps_grad_f32")
 
 
-# ------------------------------------------------------------------------------------------------ graph isomorphism conv
 # ------------------------------------------------------------------------------------------------ TemporalSampler (csrc/lstm.hip)
 def _i32(t, shape):
     assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
@@ -915,17 +985,7 @@ def lstm_unpack_add(X, x):
     check(L.load().sar_lstm_unpack_add_f32(ptr(_f32(X)), X.stride(0), ptr(_f32(x)), N, C, T, V, stream_ptr()), "sar_lstm_unpack_add_f32")
 
 
-def conv_gemm_nparts(B, V, T_src, T_out, Kc, M, taps=1, stride=1, pad=0, transposed=False, epi=L.SAR_EPI_STATS):
-    """partial sums per output row that sar_conv_gemm_f32 (TEMPORAL) writes for this geometry"""
-    d = ConvDesc()
-    d.mode, d.transposed, d.B, d.V, d.T_src, d.T_out, d.Kc, d.M = L.SAR_CONV_TEMPORAL, int(transposed), B, V, T_src, T_out, Kc, M
-    d.taps, d.stride, d.pad, d.epi = taps, stride, pad, epi
-    n = L.load().sar_conv_gemm_nparts(C.byref(d))
-    if n <= 0:
-        check(n or -1, "sar_conv_gemm_nparts")
-    return n
-
-
+# ------------------------------------------------------------------------------------------------ graph isomorphism conv
 def gin_adjacency(A, eps, table, scale, slice_scale=None, Km1=None, V=None):
     """table [Km1+1][V][V] (or None), scale[C] = 1 + eps, slice_scale[Km1+1] = (1, .., 1, 1 + eps) (or None)"""
     if A is not None:
@@ -1321,14 +1381,19 @@ def _pack_split_conv2d(W, w_stride_tap, w_stride_c, Kc, M, arith, transposed):
     operand layout (tap, m, c) of the forward tensor as the fp32 kernel takes it (element (tap, c', m') of the call = weight of
     forward tap `tap`); the stride-1 split kernel (transposed="mirror") wants the mirrored taps: item element (tap, c', m') =
     W[8 - tap][c'][m']; the stride-2 data gradient addresses the forward taps directly (no mirroring)."""
-    pk = PackedSplitWeights(arith)
     if transposed == "mirror":
-        pk.add("w", 8 * w_stride_tap, -w_stride_tap, w_stride_c, 1, 9, Kc, M)
-    else:
-        pk.add("w", 0, w_stride_tap, w_stride_c, 1, 9, Kc, M)
-    pk.finalize(W.device)
-    pk.refresh(W)
-    return pk.image("w"), pk.bound("w")
+        return _pack_split_single(W, -w_stride_tap, w_stride_c, 9, Kc, M, arith, 8 * w_stride_tap)
+    return _pack_split_single(W, w_stride_tap, w_stride_c, 9, Kc, M, arith)
+
+
+def conv2d_gemm_route(split, *, aux_even_pixels=False, epi=L.SAR_EPI_NONE, **geo):
+    """the kernel of a conv2d_gemm call: the split arithmetic (sar_conv2d_gemm_split: bf16x6 / f16x3a on the shapes of
+    conv2d_split_applicable()) or None (sar_conv2d_gemm_f32).  `split`: "default" = DEFAULT_SPLIT.  No library, no tensor."""
+    if split == "default":
+        split = DEFAULT_SPLIT
+    if split in ("f16x3a", "bf16x6") and conv2d_split_applicable(aux_even_pixels=aux_even_pixels, epi=epi, **geo):
+        return split
+    return None
 
 
 def conv2d_gemm(src, out, W, w_stride_tap, w_stride_c, *, epi=L.SAR_EPI_NONE, aux=None, aux_affine=None, aux_mean=None,
@@ -1341,10 +1406,7 @@ def conv2d_gemm(src, out, W, w_stride_tap, w_stride_c, *, epi=L.SAR_EPI_NONE, au
     ctx: an L.Context whose side streams the call may fan out over (None: the current stream only).
     kslab: a callable nfloats -> flat float32 tensor that provides the K-split workspace (None: torch.empty here)."""
     lib = L.load()
-    if split == "default":
-        split = DEFAULT_SPLIT
-    if split not in ("f16x3a", "bf16x6") or not conv2d_split_applicable(aux_even_pixels=aux_even_pixels, epi=epi, **geo):
-        split = None
+    split = conv2d_gemm_route(split, aux_even_pixels=aux_even_pixels, epi=epi, **geo)
     d = _conv2d_desc(src, **geo)
     d.ctx = ctx.handle if ctx is not None else None
     d.flags = L.SAR_C2D_AUX_EVEN_PIXELS if aux_even_pixels else 0
@@ -1355,8 +1417,7 @@ def conv2d_gemm(src, out, W, w_stride_tap, w_stride_c, *, epi=L.SAR_EPI_NONE, au
     if aux_affine is not None:
         d.aux_scale, d.aux_shift = ptr(_f32(aux_affine[0])), ptr(_f32(aux_affine[1]))
     d.aux_mean = ptr(_f32(aux_mean))
-    partials = None
-    nparts = 0
+    partials, nparts = None, 0
     if split:      # small feature maps: workspace of the K-split (sar_hip.h), 0 bytes = not planned for this shape
         nb = lib.sar_conv2d_gemm_split_slab_bytes(C.byref(d))
         if nb > 0:
@@ -1365,21 +1426,15 @@ def conv2d_gemm(src, out, W, w_stride_tap, w_stride_c, *, epi=L.SAR_EPI_NONE, au
             d.slab = ptr(kslab)
     if epi in (L.SAR_EPI_STATS, L.SAR_EPI_MASK):
         nparts = lib.sar_conv2d_gemm_split_nparts(C.byref(d)) if split else lib.sar_conv2d_nparts(C.byref(d))
-        if nparts <= 0:
-            check(nparts or -1, "sar_conv2d_nparts")
-        partials = torch.empty((geo["M"], nparts, 2), dtype=torch.float32, device=src.device)
-        d.partials = ptr(partials)
+        partials = _reducing_partials(d, nparts, "sar_conv2d_nparts", geo["M"], src.device)
     n_conv = geo["B"] * (geo["H_src"] * geo["W_src"] if geo.get("transposed") else geo["H_out"] * geo["W_out"])
     flops = 2.0 * geo["M"] * geo["Kc"] * geo["KH"] * geo["KW"] * n_conv
     tag = "conv2d_%dx%d%s" % (geo["KH"], geo["KW"], "_dgrad" if geo.get("transposed") else "")
     if split:
-        w_bound = bounds[1] if bounds is not None else None
-        if packed is None:
-            packed, w_bound = _pack_split_conv2d(W, w_stride_tap, w_stride_c, geo["Kc"], geo["M"], split,
-                                                 "mirror" if (geo.get("transposed") and geo["stride"] == 1) else False)
-        src_bound = bounds[0] if bounds is not None else None
-        if split.startswith("f16") and src_bound is None:
-            src_bound = _src_bound_single(src, geo.get("pro"))
+        mirror = "mirror" if (geo.get("transposed") and geo["stride"] == 1) else False
+        (src_bound, w_bound), packed = _split_inputs(
+            split, bounds, ((src, geo.get("pro")),), packed,
+            lambda: _pack_split_conv2d(W, w_stride_tap, w_stride_c, geo["Kc"], geo["M"], split, mirror))
         with profiler.region(tag + "_split" + _shape_tag(geo), flops):
             check(lib.sar_conv2d_gemm_split(C.byref(d), L.SAR_SPLIT[split], ptr(packed), ptr(src_bound), ptr(w_bound), stream_ptr()),
                   "sar_conv2d_gemm_split")
@@ -1397,8 +1452,7 @@ def conv2d_wgrad(src, dout, dW_tcm, *, split="default", bounds=None, slabs=None,
     stride 1 / pad 1 at image widths 8 / 16 / 32 / 64, sar_conv2d_wgrad_split (fp32 results on the fp16 / bf16 matrix pipe; bounds =
     (src_bound, dout_bound) cells, None = computed here by device kernels).  Slabs are summed in slab order either way."""
     lib = L.load()
-    if split == "default":
-        split = DEFAULT_SPLIT
+    split = DEFAULT_SPLIT if split == "default" else split
     if split not in ("f16x3a", "bf16x6"):
         split = None
     d = _conv2d_desc(src, **geo)
@@ -1409,43 +1463,27 @@ def conv2d_wgrad(src, dout, dW_tcm, *, split="default", bounds=None, slabs=None,
     if split:
         wk, kt = C.c_int(0), C.c_int(0)
         wgs = lib.sar_conv2d_wgrad_split_blocks(C.byref(d), L.SAR_SPLIT[split], C.byref(wk), C.byref(kt))
-        if wgs == L.SAR_E_UNSUP:
+        if wgs == L.SAR_E_UNSUP:      # not built for this shape: the fp32 kernel
             split = None
         else:
             check(0 if wgs > 0 else (wgs or -1), "sar_conv2d_wgrad_split_blocks")
     if split:
         ntiles = (geo["B"] * geo["H_out"] * geo["W_out"] + kt.value - 1) // kt.value
-        groups = max(1, min(ntiles, (_C2D_WG_SLOTS + wgs - 1) // wgs))      # one round of the resident workgroups (2 per CU)
-        nsplit = groups * wk.value
-        d.nsplit = nsplit
-        slab = slabs.slab(dW_tcm, nsplit, n) if slabs is not None else torch.empty((nsplit, n), dtype=torch.float32, device=src.device)
-        d.slab = ptr(slab)
-        sb, db = bounds if bounds is not None else (None, None)
-        if split.startswith("f16"):
-            if sb is None:
-                sb = _src_bound_single(src, geo.get("pro"))
-            if db is None:
-                db = _src_bound_single(dout, None)
+        nsplit = max(1, min(ntiles, (_C2D_WG_SLOTS + wgs - 1) // wgs)) * wk.value      # one round of the resident workgroups (2 per CU)
+    else:
+        wgs = ((geo["M"] + 63) // 64) * max(1, (geo["Kc"] + 31) // 32)
+        # one round of the 512 resident workgroups (2 per CU): measured 22 % faster than 768 / 1024 in isolation (the kernels do not
+        # fit 3 per CU, so a larger grid runs a second, partly filled round)
+        nsplit = max(1, min(geo["B"] * max(1, geo["H_out"] // 2), (_C2D_WG_SLOTS + wgs - 1) // wgs))
+    slab = _wgrad_slab(d, slabs, dW_tcm, nsplit, n, src.device)
+    if split:
+        (sb, db), _ = _split_inputs(split, bounds, ((src, geo.get("pro")), (dout, None)))
         with profiler.region("conv2d_wgrad_3x3_split" + _shape_tag(geo), flops):
             check(lib.sar_conv2d_wgrad_split(C.byref(d), L.SAR_SPLIT[split], ptr(sb), ptr(db), stream_ptr()), "sar_conv2d_wgrad_split")
-        if slabs is not None:
-            slabs.add(slab, nsplit, n, dW_tcm)
-        else:
-            check(lib.sar_slab_reduce_f32(ptr(slab), nsplit, n, n, ptr(dW_tcm), stream_ptr()), "sar_slab_reduce_f32")
-        return
-    wgs = ((geo["M"] + 63) // 64) * max(1, (geo["Kc"] + 31) // 32)
-    # one round of the 512 resident workgroups (2 per CU): measured 22 % faster than 768 / 1024 in isolation (the kernels do not
-    # fit 3 per CU, so a larger grid runs a second, partly filled round)
-    nsplit = max(1, min(geo["B"] * max(1, geo["H_out"] // 2), (_C2D_WG_SLOTS + wgs - 1) // wgs))
-    d.nsplit = nsplit
-    slab = slabs.slab(dW_tcm, nsplit, n) if slabs is not None else torch.empty((nsplit, n), dtype=torch.float32, device=src.device)
-    d.slab = ptr(slab)
-    with profiler.region("conv2d_wgrad_%dx%d" % (geo["KH"], geo["KW"]) + _shape_tag(geo), flops):
-        check(lib.sar_conv2d_wgrad_f32(C.byref(d), stream_ptr()), "sar_conv2d_wgrad_f32")
-    if slabs is not None:
-        slabs.add(slab, nsplit, n, dW_tcm)
     else:
-        check(lib.sar_slab_reduce_f32(ptr(slab), nsplit, n, n, ptr(dW_tcm), stream_ptr()), "sar_slab_reduce_f32")
+        with profiler.region("conv2d_wgrad_%dx%d" % (geo["KH"], geo["KW"]) + _shape_tag(geo), flops):
+            check(lib.sar_conv2d_wgrad_f32(C.byref(d), stream_ptr()), "sar_conv2d_wgrad_f32")
+    _wgrad_slab_done(slabs, slab, nsplit, n, dW_tcm)
 
 
 def permute3(inp, out, d0, d1, d2, s0, s1, s2):

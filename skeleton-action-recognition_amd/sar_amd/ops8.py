@@ -4,14 +4,14 @@ A CN8 activation is a torch.bfloat16 tensor of shape (G, ld, 8): G = ceil(C/8) p
 (g, col) = channels 8g..8g+7 of column col = (b*T + t)*V + v.  torch is used for device memory and the stream only.
 """
 import ctypes as C
-
 import os
 
 import torch
 
 from . import _lib as L
 from . import profiler
-from ._lib import ConvDesc, WgradDesc, check, ptr, stream_ptr
+from ._lib import check, ptr, stream_ptr
+from .ops import _REDUCING, _conv_desc, _data_bn_dx_out, _reducing_partials, _wgrad_desc, _wgrad_slab, _wgrad_slab_done
 
 _MFMA_GATHER = os.environ.get("SAR_CN8_MFMA_GATHER", "1") == "1"   # A/B switch: 0 keeps the vector-ALU gather of the dense adjacency slice
 
@@ -58,6 +58,9 @@ def to_cn(x8, channels, n=None, out=None):
     return out
 
 
+_CN8 = (lambda t: (ptr(_cn8(t)), t.shape[1]), _f32)      # a CN8 operand -> (pointer, leading dimension in units); a per-channel vector
+
+
 def conv_gemm(mode, src, out, packed, *, B, V, T_src, T_out, Kc, M, taps, stride=1, pad=0, transposed=False, bias=None,
               pro=None, pro_relu=False, tables=None, epi=L.SAR_EPI_NONE, aux=None, aux_affine=None, aux_mean=None, aux2=None,
               aux_mask=None):
@@ -65,40 +68,19 @@ def conv_gemm(mode, src, out, packed, *, B, V, T_src, T_out, Kc, M, taps, stride
     (partials, nparts) when the epilogue reduces.  SAR_EPI_ADD_GATE (graph data gradient): out = gate(acc + aux) with the gate
     bytes `aux_mask`, partial sums (sum out, sum out (aux2 - aux_mean))."""
     lib = L.load()
-    d = ConvDesc()
-    d.mode, d.transposed, d.B, d.V = mode, int(transposed), B, V
-    d.T_src, d.T_out, d.Kc, d.M = T_src, T_out, Kc, M
-    d.taps, d.stride, d.pad, d.pro_relu, d.epi = taps, stride, pad, int(pro_relu), epi
     _cn8(src), _cn8(out), _cn8(aux)
-    assert src.shape[0] == (Kc + 7) // 8 and out.shape[0] == (M + 7) // 8
-    d.src, d.ld_src = ptr(src), src.shape[1]
-    d.out, d.ld_out = ptr(out), out.shape[1]
-    d.bias = ptr(_f32(bias))
-    if pro is not None:
-        d.pro_scale, d.pro_shift = ptr(_f32(pro[0])), ptr(_f32(pro[1]))
-    if tables is not None:
-        d.g_idx, d.g_wt, d.g_colsum = ptr(tables.idx), ptr(tables.wt), ptr(tables.colsum)
-        d.g_flags = getattr(tables, "g_flags", 0) if _MFMA_GATHER else 0
-        for i in range(3):
-            d.nz[i] = tables.nz[i]
-    if aux is not None:
-        assert aux.shape[0] == out.shape[0]
-        d.aux, d.ld_aux = ptr(aux), aux.shape[1]
-    if aux_affine is not None:
-        d.aux_scale, d.aux_shift = ptr(_f32(aux_affine[0])), ptr(_f32(aux_affine[1]))
-    d.aux_mean = ptr(_f32(aux_mean))
+    assert src.shape[0] == (Kc + 7) // 8 and out.shape[0] == (M + 7) // 8 and (aux is None or aux.shape[0] == out.shape[0])
+    d = _conv_desc(_CN8, mode, src, out, B, V, T_src, T_out, Kc, M, taps, stride, pad, transposed, epi, pro, pro_relu, tables,
+                   getattr(tables, "g_flags", 0) if _MFMA_GATHER else 0, bias, aux, aux_affine, aux_mean)
     if epi == L.SAR_EPI_ADD_GATE:
         assert aux2 is not None and aux_mask is not None and aux_mean is not None and aux2.shape[0] == out.shape[0]
         assert aux_mask.dtype == torch.uint8 and aux_mask.shape == (out.shape[0], aux2.shape[1]) and aux_mask.is_contiguous()
         _cn8(aux2)
         d.aux2, d.ld_aux2, d.aux_mask = ptr(aux2), aux2.shape[1], ptr(aux_mask)
     partials, nparts = None, 0
-    if epi in (L.SAR_EPI_STATS, L.SAR_EPI_MASK, L.SAR_EPI_ADD_GATE):
+    if epi in _REDUCING:
         nparts = lib.sar_conv_gemm_cn8_nparts(C.byref(d))
-        if nparts <= 0:
-            check(nparts or -1, "sar_conv_gemm_cn8_nparts")
-        partials = torch.empty((M, nparts, 2), dtype=torch.float32, device=src.device)
-        d.partials = ptr(partials)
+        partials = _reducing_partials(d, nparts, "sar_conv_gemm_cn8_nparts", M, src.device)
     n_conv = B * (T_src if transposed else T_out) * V
     tag = ("gemm_graph" if mode == L.SAR_CONV_GRAPH else ("gemm_temporal%d%s" % (taps, "_dgrad" if transposed else ""))) + "_cn8"
     with profiler.region(tag, 2.0 * M * Kc * taps * n_conv, 2.0 * (Kc * B * T_src * V + M * B * T_out * V)):
@@ -106,7 +88,7 @@ def conv_gemm(mode, src, out, packed, *, B, V, T_src, T_out, Kc, M, taps, stride
     return (partials, nparts) if partials is not None else None
 
 
-_WGRAD_SLOTS = int(__import__("os").environ.get("SAR_WGRAD8_SLOTS", "512"))
+_WGRAD_SLOTS = int(os.environ.get("SAR_WGRAD8_SLOTS", "512"))
 
 
 def conv_wgrad(mode, src, dout, dW_out, *, B, V, T_src, T_out, Kc, M, taps, stride=1, pad=0, pro=None, pro_relu=False,
@@ -114,40 +96,20 @@ def conv_wgrad(mode, src, dout, dW_out, *, B, V, T_src, T_out, Kc, M, taps, stri
     """sar_conv_wgrad_cn8 + sar_slab_reduce_f32: dW (and dbias right behind it) -> dW_out[0 : wsize + bsize] (flat fp32).
     slabs (ops.SlabBatch): the slabs are summed by the batch's next flush() instead of by a launch of their own."""
     lib = L.load()
-    d = WgradDesc()
-    d.mode, d.B, d.V, d.T_src, d.T_out, d.Kc, d.M = mode, B, V, T_src, T_out, Kc, M
-    d.taps, d.stride, d.pad, d.pro_relu = taps, stride, pad, int(pro_relu)
-    ft = lib.sar_conv_wgrad_cn8_tile_frames(mode)
-    ntiles = B * ((T_out + ft - 1) // ft)
-    cb = 32 if (mode == L.SAR_CONV_TEMPORAL and taps == 9) else 64
-    blocks = ((M + 63) // 64) * ((Kc + cb - 1) // cb)
+    d = _wgrad_desc(_CN8, mode, src, dout, B, V, T_src, T_out, Kc, M, taps, stride, pad, pro, pro_relu, tables,
+                    getattr(tables, "g_flags", 0) if _MFMA_GATHER else 0, w_stride_tap, w_stride_c, wsize, bsize)
     if nsplit is None:           # two resident workgroups per CU (SAR_WGRAD8_SLOTS: sweep knob, tools)
+        ft = lib.sar_conv_wgrad_cn8_tile_frames(mode)
+        ntiles = B * ((T_out + ft - 1) // ft)
+        cb = 32 if (mode == L.SAR_CONV_TEMPORAL and taps == 9) else 64
+        blocks = ((M + 63) // 64) * ((Kc + cb - 1) // cb)
         nsplit = max(1, min(ntiles, (_WGRAD_SLOTS + blocks - 1) // blocks))
-    d.nsplit = nsplit
-    _cn8(src), _cn8(dout)
-    d.src, d.ld_src, d.dout, d.ld_dout = ptr(src), src.shape[1], ptr(dout), dout.shape[1]
-    if pro is not None:
-        d.pro_scale, d.pro_shift = ptr(_f32(pro[0])), ptr(_f32(pro[1]))
-    ident = 0
-    if tables is not None:
-        d.g_idx, d.g_wt, d.g_colsum = ptr(tables.idx), ptr(tables.wt), ptr(tables.colsum)
-        d.g_flags = getattr(tables, "g_flags", 0) if _MFMA_GATHER else 0
-        for i in range(3):
-            d.nz[i] = tables.nz[i]
-        ident = int(getattr(tables, "slice0_identity", False))
-    d.w_stride_tap, d.w_stride_c, d.wsize, d.bsize = w_stride_tap, w_stride_c, wsize, bsize
-    assert dW_out.numel() >= wsize + bsize and dW_out.is_contiguous()
-    slab = (slabs.slab(dW_out, nsplit, wsize + bsize) if slabs is not None
-            else torch.empty((nsplit, wsize + bsize), dtype=torch.float32, device=src.device))
-    d.slab = ptr(slab)
+    ident, n = (int(getattr(tables, "slice0_identity", False)) if tables is not None else 0), wsize + bsize
+    slab = _wgrad_slab(d, slabs, dW_out, nsplit, n, src.device)
     tag = ("wgrad_graph" if mode == L.SAR_CONV_GRAPH else "wgrad_temporal%d" % taps) + "_cn8"
     with profiler.region(tag, 2.0 * M * Kc * taps * B * T_out * V, 2.0 * (Kc * B * T_src * V + M * B * T_out * V)):
         check(lib.sar_conv_wgrad_cn8(C.byref(d), ident, stream_ptr()), "sar_conv_wgrad_cn8")
-    if slabs is not None:
-        slabs.add(slab, nsplit, wsize + bsize, dW_out)
-        return
-    check(lib.sar_slab_reduce_f32(ptr(slab), nsplit, wsize + bsize, wsize + bsize, ptr(dW_out), stream_ptr()),
-          "sar_slab_reduce_f32")
+    _wgrad_slab_done(slabs, slab, nsplit, n, dW_out)
 
 
 def relu_mask(channels, n, device):
@@ -162,7 +124,7 @@ def bn_add_relu_fwd(u, sc, sh, res_kind, r, rsc, rsh, y, channels, mask=None, n=
                                            ptr(mask), channels, n, u.shape[1], stream_ptr()), "sar_bn_add_relu_fwd_cn8")
 
 
-_REDUCE_CHUNK = int(__import__("os").environ.get("SAR_BWD_REDUCE_CHUNK8", "8192"))     # units per workgroup of the BN-backward reduction
+_REDUCE_CHUNK = int(os.environ.get("SAR_BWD_REDUCE_CHUNK8", "8192"))     # units per workgroup of the BN-backward reduction
 
 
 def bn_add_relu_bwd_reduce(dy, y, u, r, channels, mu=None, mr=None, tail=None, mask=None, n=None):
@@ -212,7 +174,6 @@ def data_bn_bwd_reduce(x, bone_parent, dy, mean, partials, motion=False):
 
 def data_bn_bwd_apply(x, bone_parent, dy, k, dx=None, motion=False):
     """ops.data_bn_bwd_apply with dy = the (C <= 8)-channel CN8 plane; dx is float32 (N, C, T, V, M)"""
-    from .ops import _data_bn_dx_out
     dx = _data_bn_dx_out(x, dx)
     N, C_, T, V, M = x.shape
     check(L.load().sar_data_bn_bwd_apply_cn8(ptr(x), N, C_, T, V, M, ptr(bone_parent), int(motion), ptr(_cn8(dy)), dy.shape[1],
