@@ -1024,6 +1024,48 @@ int sar_lstm_pack_f32(const float* x, float* X, int64_t ld, int N, int C, int T,
 int sar_lstm_unpack_add_f32(const float* X, int64_t ld, float* x, int N, int C, int T, int V, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * TemporalAttention(num_hidden) (models/stgcn.py:67-85): a per-frame gate.  An MLP over the V*C features of a frame,
+ * f[r, v*C + c] = x[n, c, t, v] with r = n*T + t (the reference transposes to (N, T, V, C) before its reshape), ends in
+ * Dense(1, sigmoid); every joint and channel of the frame is multiplied by the result.  csrc/tattn.hip, fp32; the three products
+ * run on v_mfma_f32_32x32x2_f32.
+ * A strided tensor is passed as (pointer, s_n, s_c): element (n, c, t, v) at n*s_n + c*s_c + t*V + v -- NCHW: s_n = C*T*V,
+ * s_c = T*V; a CN matrix [C][ld]: s_n = T*V, s_c = ld (as GPool above).  The runs of T*V floats may not overlap.  x and dout are
+ * read where they lie: no packed or transposed copy is made.  kernel = mlp.0.kernel (V*C, units) contiguous (Keras layout, row
+ * v*C + c), bias (units).  The hidden activations are CN matrices [units][ld] with columns r, ld >= N*T; a, dz of the last layer: [N*T].
+ * Limits (SAR_E_ARG / SAR_E_UNSUP before any launch): 1 <= units <= SAR_TATTN_UMAX, 1 <= V <= SAR_TATTN_VMAX, any C >= 1,
+ * N*T < 2^22, N*C*T*V < 2^31.  No atomics: repeated launches are bitwise equal, and a row's result depends on the row's data only.
+ *   sar_tattn_score_f32    models/stgcn.py:77-81: h[j][r] = act(sum_{c,v} kernel[v*C + c][j] x[n, c, t, v] + bias[j]); act =
+ *                          SAR_TATTN_RELU (a hidden Dense) or SAR_TATTN_SIGMOID (the closing Dense(1, sigmoid), when num_hidden = [])
+ *   sar_tattn_act_f32      the activation of a later layer, in place on rows x n elements of z [rows][ld] (its product is
+ *                          sar_conv_gemm_f32 as a 1x1 convolution; models/stgcn.py:72-75)
+ *   sar_tattn_scale_f32    models/stgcn.py:83-84: out[n, c, t, v] = x[n, c, t, v] a[n*T + t]
+ *   sar_tattn_dscore_f32   dz[r] = (sum_{c,v} dout[n, c, t, v] x[n, c, t, v]) a[r] (1 - a[r]): the gradient at the last layer's
+ *                          pre-activation.  One fp32 fmaf chain over c per (t, v), the V chains of a frame added in order in fp64
+ *   sar_tattn_dact_f32     dh[i][r] = 0 where h[i][r] <= 0, in place (ReLU's gradient, 0 at 0 as TensorFlow)
+ *   sar_tattn_wgrad_f32    slab[s] = this slab's share of dkernel [V*C][units] | dbias [units]: dkernel[v*C + c][j] = sum_r
+ *                          x[n, c, t, v] dz[j][r], dbias[j] = sum_r dz[j][r].  nslab = sar_tattn_wgrad_slabs(N, C, T, V) (a function
+ *                          of the shape alone); slab stride V*C*units + units; every element of every slab is written; add the
+ *                          slabs with sar_slab_reduce_f32
+ *   sar_tattn_dx_f32       dx[n, c, t, v] = dout[n, c, t, v] a[r] + sum_j kernel[v*C + c][j] dz[j][r]  (every element written
+ *                          once; dx may not be dout) */
+#define SAR_TATTN_UMAX 128
+#define SAR_TATTN_VMAX 64
+enum { SAR_TATTN_RELU = 0, SAR_TATTN_SIGMOID = 1 };
+int sar_tattn_score_f32(const float* x, int64_t s_n, int64_t s_c, const float* kernel, const float* bias, int N, int C, int T, int V,
+                        int units, int act, float* h, int64_t ld_h, sar_stream_t s);
+int sar_tattn_act_f32(float* z, int64_t ld, int rows, int64_t n, int act, sar_stream_t s);
+int sar_tattn_scale_f32(const float* x, int64_t s_n, int64_t s_c, const float* a, int N, int C, int T, int V, float* out, int64_t o_sn,
+                        int64_t o_sc, sar_stream_t s);
+int sar_tattn_dscore_f32(const float* x, int64_t s_n, int64_t s_c, const float* dout, int64_t d_sn, int64_t d_sc, const float* a, int N,
+                         int C, int T, int V, float* dz, sar_stream_t s);
+int sar_tattn_dact_f32(const float* h, int64_t ld_h, float* dh, int64_t ld_dh, int rows, int64_t n, sar_stream_t s);
+int sar_tattn_wgrad_slabs(int N, int C, int T, int V);
+int sar_tattn_wgrad_f32(const float* x, int64_t s_n, int64_t s_c, const float* dz, int64_t ld_dz, int N, int C, int T, int V, int units,
+                        float* slab, int nslab, sar_stream_t s);
+int sar_tattn_dx_f32(const float* dout, int64_t d_sn, int64_t d_sc, const float* a, const float* kernel, const float* dz, int64_t ld_dz,
+                     int N, int C, int T, int V, int units, float* dx, int64_t g_sn, int64_t g_sc, sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * Box calibration (csrc/box_probe.hip; bench.py's "box" object -- no reference counterpart, measurement only): what the box
  * this process landed on sustains, so that a line's `frac` (against the guide's peaks) can be read next to `frac_of_box`.
  *   sar_box_mfma        dense loop of one matrix instruction: kind 0 = v_mfma_f32_32x32x2_f32, 1 = v_mfma_f32_32x32x16_f16,

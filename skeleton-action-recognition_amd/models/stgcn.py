@@ -13,11 +13,20 @@ autograd node whose forward and backward are the ENGINE's block code (STGCN.bloc
 the folded BN + ReLU prologue of the temporal convolution, the statistics epilogues, bn_add_relu with the 1-bit mask and the matching
 backward passes).  It converts NCHW <-> CN at its boundary and copies its parameters into the engine per call, so a network composed
 of these layers pays that per layer where `Model` does not: an interface, not the fast path.
+
+`TemporalAttention(num_hidden)` (models/stgcn.py:67-85) is the per-frame gate: an MLP over the V C features of a frame ends in
+Dense(1, sigmoid), and every joint and channel of the frame is multiplied by the result.  One autograd node over
+sar_amd.ops.tattn_forward / tattn_backward (csrc/tattn.hip): the first Dense, its weight gradient and the input gradient are fp32 MFMA
+kernels that read x where it lies (no transposed copy), the later layers are the library's 1x1 products.  Not wired into main_gnn.py
+(the reference wires it into no model); in front of `Model` it trains under one optimizer, the engines return d loss / d clip.
 """
+import math
+
 import numpy as np
 import torch
 
 from models.gcn import GraphConvTD, _require, from_cn, to_cn, variance_scaling_
+from sar_amd import ops
 from sar_amd.graph_tables import gather_lists
 from sar_amd.stgcn import STGCN, BLOCKS, KS, KT  # noqa: F401
 
@@ -257,3 +266,86 @@ class SpatioTemporalGraphConv(torch.nn.Module):
             y, To, _ = eng.block_forward(0, to_cn(x), B, T, False)
             return from_cn(y, (B, self.filters, To, V)), A
         return _BlockFunction.apply(x, A, self, eng, *[t for _, t in self._names()]), A
+
+
+class _TemporalAttentionFn(torch.autograd.Function):
+    """TemporalAttention as one node; params = (kernel, bias) per layer"""
+
+    @staticmethod
+    def forward(ctx, x, save, *params):
+        out, saved = ops.tattn_forward(x, params)
+        if save:
+            ctx.save_for_backward(x, *saved, *params)
+            ctx.nsaved = len(saved)
+        a = saved[0]
+        ctx.mark_non_differentiable(a)
+        return out, a
+
+    @staticmethod
+    def backward(ctx, dout, _da):
+        x, rest = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        saved, params = rest[:ctx.nsaved], rest[ctx.nsaved:]
+        dx, grads = ops.tattn_backward(x, saved, params, dout.contiguous(), need_dx=ctx.needs_input_grad[0])
+        return (dx, None) + tuple(grads)
+
+
+class _Dense(torch.nn.Module):
+    """tf.keras.layers.Dense(units)'s variables in the Keras layouts -- kernel (in, units), bias (units) --, created on the first call
+    (or by load_state_dict) with the Keras default initialisers: glorot_uniform, zeros"""
+
+    def __init__(self, units):
+        super().__init__()
+        self.units = int(units)
+        self.register_parameter("kernel", None)
+        self.register_parameter("bias", None)
+
+    def build(self, in_features, device):
+        if self.kernel is None:
+            limit = math.sqrt(6.0 / (in_features + self.units))
+            kernel = (torch.rand(int(in_features), self.units, dtype=torch.float64) * 2 - 1) * limit
+            self.kernel = torch.nn.Parameter(kernel.to(torch.float32).to(device))
+            self.bias = torch.nn.Parameter(torch.zeros(self.units, dtype=torch.float32, device=device))
+        elif self.kernel.shape[0] != in_features:
+            raise ValueError("the layer was built for %d input features, got %d" % (self.kernel.shape[0], in_features))
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        k = state_dict.get(prefix + "kernel")
+        if self.kernel is None and k is not None:
+            self.build(k.shape[0], k.device if k.is_cuda else "cuda")
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+
+class TemporalAttention(torch.nn.Module):
+    """models/stgcn.py:67-85; see the module docstring.  forward(x (N, C, T, V), training) -> (N, C, T, V); `training` changes nothing
+    (no dropout, no BatchNorm) and is kept for the signature.  Parameters: mlp.{i}.kernel (in, units), mlp.{i}.bias (units), widths
+    num_hidden + [1], the first `in` = V C with feature index v C + c.  After a call `last_attention` (N, T) holds the gate (detached).
+    Limits (ValueError before anything is built or launched): x a contiguous float32 CUDA tensor, V <= 64, every width <= 128,
+    N T < 2^22."""
+
+    def __init__(self, num_hidden):
+        super().__init__()
+        widths = [int(w) for w in num_hidden] + [1]
+        if any(w < 1 or w > ops.TATTN_UMAX for w in widths):
+            raise ValueError("the kernels are built for 1 <= units <= %d, got %r" % (ops.TATTN_UMAX, list(num_hidden)))
+        self.num_hidden = list(num_hidden)
+        self.mlp = torch.nn.ModuleList(_Dense(w) for w in widths)
+        self.last_attention = None
+
+    def forward(self, x, training=None):
+        _require(x, 4, "x (N, C, T, V)")
+        N, C, T, V = x.shape
+        if min(N, C, T, V) < 1 or V > ops.TATTN_VMAX:
+            raise ValueError("need a non-empty x with V <= %d, got %s" % (ops.TATTN_VMAX, tuple(x.shape)))
+        if T * N >= 1 << 22:
+            raise ValueError("N T = %d rows: the kernels are built for fewer than 2^22" % (T * N))
+        if self.mlp[0].kernel is not None and self.mlp[0].kernel.shape[0] != V * C:
+            raise ValueError("the layer was built for %d input features, got V C = %d" % (self.mlp[0].kernel.shape[0], V * C))
+        features = V * C
+        for layer in self.mlp:
+            layer.build(features, x.device)
+            features = layer.units
+        params = [t for layer in self.mlp for t in (layer.kernel, layer.bias)]
+        save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+        out, a = _TemporalAttentionFn.apply(x, save, *params)
+        self.last_attention = a.detach().view(N, T)
+        return out

@@ -245,6 +245,15 @@ SIGNATURES = {
     "sar_frame_gather_bwd_f32": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i64, _i64, _fp, _i, _i, _i, _i, _i, _fp]),
     "sar_lstm_pack_f32": (_i, [_fp, _fp, _i64, _i, _i, _i, _i, _fp]),
     "sar_lstm_unpack_add_f32": (_i, [_fp, _i64, _fp, _i, _i, _i, _i, _fp]),
+    # TemporalAttention: the first Dense over the frame's V C features, the gate, their gradients (csrc/tattn.hip)
+    "sar_tattn_score_f32": (_i, [_fp, _i64, _i64, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _i64, _fp]),
+    "sar_tattn_act_f32": (_i, [_fp, _i64, _i, _i64, _i, _fp]),
+    "sar_tattn_scale_f32": (_i, [_fp, _i64, _i64, _fp, _i, _i, _i, _i, _fp, _i64, _i64, _fp]),
+    "sar_tattn_dscore_f32": (_i, [_fp, _i64, _i64, _fp, _i64, _i64, _fp, _i, _i, _i, _i, _fp, _fp]),
+    "sar_tattn_dact_f32": (_i, [_fp, _i64, _fp, _i64, _i, _i64, _fp]),
+    "sar_tattn_wgrad_slabs": (_i, [_i, _i, _i, _i]),
+    "sar_tattn_wgrad_f32": (_i, [_fp, _i64, _i64, _fp, _i64, _i, _i, _i, _i, _i, _fp, _i, _fp]),
+    "sar_tattn_dx_f32": (_i, [_fp, _i64, _i64, _fp, _fp, _fp, _i64, _i, _i, _i, _i, _i, _fp, _i64, _i64, _fp]),
     # box calibration (bench.py "box"; csrc/box_probe.hip)
     "sar_box_mfma": (_i, [_i, _i, _i, _fp, _fp, _fp]),
     "sar_box_mfma_flops": (_i64, [_i, _i, _i]),

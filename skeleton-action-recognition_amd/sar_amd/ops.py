@@ -1335,6 +1335,137 @@ def gpool_backward(x, A, saved, dout, dA_out, dx=None):
     return dx, dp, dA
 
 
+# ------------------------------------------------------------------------------------------------ TemporalAttention
+# csrc/tattn.hip (include/sar_hip.h: TemporalAttention).  x / out / dout / dx are 4-D (N, C, T, V) tensors or views whose two inner
+# strides are (V, 1), as GPool's.  params = [kernel_1, bias_1, .., kernel_L, bias_L] in the Keras layouts, kernel_i (in, units),
+# in_1 = V C with row v C + c, units_L = 1.  The hidden activations are CN matrices [units][N T]
+TATTN_UMAX, TATTN_VMAX = 128, 64
+TATTN_RELU, TATTN_SIGMOID = 0, 1
+
+
+def _tattn_check(x, params):
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
+        raise ValueError("x must be 4-D (N, C, T, V)")
+    N, C, T, V = x.shape
+    if min(N, C, T, V) < 1 or V > TATTN_VMAX:
+        raise ValueError("TemporalAttention is built for a non-empty x with V <= %d (got %s)" % (TATTN_VMAX, tuple(x.shape)))
+    if N * T >= 1 << 22 or N * C * T * V >= 1 << 31:
+        raise ValueError("TemporalAttention is built for N T < 2^22 and fewer than 2^31 elements (got %s)" % (tuple(x.shape),))
+    params = list(params)
+    if not params or len(params) % 2 or not all(isinstance(p, torch.Tensor) for p in params):
+        raise ValueError("params must be [kernel_1, bias_1, .., kernel_L, bias_L] with L >= 1")
+    features = V * C
+    for i in range(0, len(params), 2):
+        kernel, bias = params[i], params[i + 1]
+        if not (kernel.dim() == 2 and kernel.shape[0] == features and tuple(bias.shape) == (kernel.shape[1],)
+                and kernel.is_contiguous() and bias.is_contiguous()):
+            raise ValueError("layer %d: need a contiguous kernel (%d, units) and bias (units), got %s and %s"
+                             % (i // 2, features, tuple(kernel.shape), tuple(bias.shape)))
+        features = kernel.shape[1]
+        if not 1 <= features <= TATTN_UMAX:
+            raise ValueError("layer %d: the kernels are built for 1 <= units <= %d (got %d)" % (i // 2, TATTN_UMAX, features))
+    if features != 1:
+        raise ValueError("the last layer must have one unit (Dense(1, sigmoid)), got %d" % features)
+    return N, C, T, V, params
+
+
+def _tattn_device(ts):
+    for t in ts:
+        if not (t.is_cuda and t.dtype == torch.float32):
+            raise ValueError("TemporalAttention operands must be float32 CUDA tensors (got %s on %s)" % (t.dtype, t.device))
+
+
+def _tattn_geo(N, T):
+    """a (B, T', V') factorisation of the N T columns with V' <= 64 for the 1x1 products of the later layers"""
+    vf = max(d for d in range(1, min(T, 64) + 1) if T % d == 0)
+    return dict(B=N, V=vf, T_src=T // vf, T_out=T // vf)
+
+
+def tattn_forward(x, params, out=None):
+    """TemporalAttention forward (models/stgcn.py:75-85) of x (N, C, T, V), a tensor or a strided view.  Returns (out, saved); `out` may
+    be given as a view of the caller's buffer.  saved = (a (N T), h_1 (units_1, N T), .., h_{L-1}): the gate and the hidden
+    activations, what tattn_backward needs besides x and params."""
+    N, C, T, V, params = _tattn_check(x, params)
+    sn, sc = _gpool_view(x, (N, C, T, V), "x")
+    if out is not None:
+        on, oc = _gpool_view(out, (N, C, T, V), "out")
+    _tattn_device([x] + params + ([out] if out is not None else []))
+    dev, n, nl = x.device, N * T, len(params) // 2
+    if out is None:
+        out = torch.empty((N, C, T, V), dtype=torch.float32, device=dev)
+        on, oc = _gpool_view(out, (N, C, T, V), "out")
+    lib, st, geo = L.load(), stream_ptr(), _tattn_geo(N, T)
+    u = params[0].shape[1]
+    h = torch.empty((u, n), dtype=torch.float32, device=dev)
+    check(lib.sar_tattn_score_f32(ptr(x), sn, sc, ptr(params[0]), ptr(params[1]), N, C, T, V, u, TATTN_SIGMOID if nl == 1 else TATTN_RELU,
+                                  ptr(h), n, st), "sar_tattn_score_f32")
+    hs = []
+    for i in range(1, nl):
+        hs.append(h)
+        kernel, bias = params[2 * i], params[2 * i + 1]
+        cin, u = kernel.shape
+        z = torch.empty((u, n), dtype=torch.float32, device=dev)
+        conv_gemm(L.SAR_CONV_TEMPORAL, h, z, kernel, 0, u, Kc=cin, M=u, taps=1, stride=1, pad=0, bias=bias, split=None, **geo)
+        check(lib.sar_tattn_act_f32(ptr(z), n, u, n, TATTN_SIGMOID if i == nl - 1 else TATTN_RELU, st), "sar_tattn_act_f32")
+        h = z
+    a = h.view(n)
+    check(lib.sar_tattn_scale_f32(ptr(x), sn, sc, ptr(a), N, C, T, V, ptr(out), on, oc, st), "sar_tattn_scale_f32")
+    return out, (a,) + tuple(hs)
+
+
+def tattn_backward(x, saved, params, dout, need_dx=True, dx=None, keep=None):
+    """Backward of tattn_forward from dout (N, C, T, V; tensor or strided view).  Returns (dx | None, grads): grads in the order of
+    params; dx (every element written; may be given as a view of the caller's buffer) only with need_dx -- without it the input
+    gradient's product is not launched.  keep: a dict that receives the gradients at the last and the first pre-activation, "dz_L"
+    (1, N T) and "dz_1" (units_1, N T), for the tests."""
+    N, C, T, V, params = _tattn_check(x, params)
+    sn, sc = _gpool_view(x, (N, C, T, V), "x")
+    dn, dc = _gpool_view(dout, (N, C, T, V), "dout")
+    if need_dx and dx is not None:
+        gn, gc = _gpool_view(dx, (N, C, T, V), "dx")
+    n, nl = N * T, len(params) // 2
+    a, hs = saved[0], list(saved[1:])
+    if len(hs) != nl - 1 or a.numel() != n or any(tuple(h.shape) != (params[2 * i].shape[1], n) for i, h in enumerate(hs)):
+        raise ValueError("saved does not belong to these params and this x")
+    _tattn_device([x, dout, a] + hs + params + ([dx] if need_dx and dx is not None else []))
+    dev = x.device
+    lib, st, geo = L.load(), stream_ptr(), _tattn_geo(N, T)
+    dz = torch.empty((1, n), dtype=torch.float32, device=dev)
+    check(lib.sar_tattn_dscore_f32(ptr(x), sn, sc, ptr(dout), dn, dc, ptr(a), N, C, T, V, ptr(dz), st), "sar_tattn_dscore_f32")
+    grads = [None] * len(params)
+    if keep is not None:
+        keep["dz_L"] = dz
+    for i in range(nl - 1, 0, -1):
+        kernel, h = params[2 * i], hs[i - 1]
+        cin, u = kernel.shape
+        flat = torch.empty(cin * u + u, dtype=torch.float32, device=dev)
+        conv_wgrad(L.SAR_CONV_TEMPORAL, h, dz, flat, Kc=cin, M=u, taps=1, stride=1, pad=0, w_stride_tap=0, w_stride_c=u, wsize=cin * u,
+                   bsize=u, split=None, **geo)
+        grads[2 * i], grads[2 * i + 1] = flat[:cin * u].view(cin, u), flat[cin * u:]
+        WT = torch.empty((u, cin), dtype=torch.float32, device=dev)
+        transpose(kernel, WT, 1, cin, u)
+        dh = torch.empty((cin, n), dtype=torch.float32, device=dev)
+        conv_gemm(L.SAR_CONV_TEMPORAL, dz, dh, WT, 0, cin, Kc=u, M=cin, taps=1, stride=1, pad=0, transposed=True, split=None, **geo)
+        check(lib.sar_tattn_dact_f32(ptr(h), n, ptr(dh), n, cin, n, st), "sar_tattn_dact_f32")
+        dz = dh
+    if keep is not None:
+        keep["dz_1"] = dz
+    kernel = params[0]
+    u, size = kernel.shape[1], kernel.numel() + kernel.shape[1]
+    nslab = lib.sar_tattn_wgrad_slabs(N, C, T, V)
+    slab, flat = torch.empty((nslab, size), dtype=torch.float32, device=dev), torch.empty(size, dtype=torch.float32, device=dev)
+    check(lib.sar_tattn_wgrad_f32(ptr(x), sn, sc, ptr(dz), n, N, C, T, V, u, ptr(slab), nslab, st), "sar_tattn_wgrad_f32")
+    check(lib.sar_slab_reduce_f32(ptr(slab), nslab, size, size, ptr(flat), st), "sar_slab_reduce_f32")
+    grads[0], grads[1] = flat[:kernel.numel()].view(kernel.shape), flat[kernel.numel():]
+    if not need_dx:
+        return None, grads
+    if dx is None:
+        dx = torch.empty((N, C, T, V), dtype=torch.float32, device=dev)
+        gn, gc = _gpool_view(dx, (N, C, T, V), "dx")
+    check(lib.sar_tattn_dx_f32(ptr(dout), dn, dc, ptr(a), ptr(kernel), ptr(dz), n, N, C, T, V, u, ptr(dx), gn, gc, st), "sar_tattn_dx_f32")
+    return dx, grads
+
+
 # ------------------------------------------------------------------------------------------------ ResNet-18 ops
 def _shape_tag(geo):
     """SAR_PROFILE_SHAPES=1 (diagnostic, tools/pathb_layers.py): one profiler bucket per layer geometry"""
