@@ -11,7 +11,12 @@ NaN around inputs, -7.25 around outputs, 0xA5 around mask bytes.  Each kernel ru
   4. every output and every reduction partial is finite: no NaN of an input's padding reached a result;
   5. where the ABI rejects the leading dimension, the call raises (or relu_mask returns None) and the outputs hold only the fill.
 
-The guards are part of the operand's own allocation, so a stray access shows as a failed assertion, never as a fault."""
+The guards are part of the operand's own allocation, so a stray access shows as a failed assertion, never as a fault.
+
+Rectangular and odd-sized 2-D cases (tests/conv2d_rect_cases.py): groups A and E whole, one case each of B, C and F.  Worst error over
+the 2-D cases of this file, MEASURED on an MI355X, every launch bitwise equal to the tight one: A masked data gradient 5.2e-7, its sums
+2.6e-7 / 3.7e-7, with the compact aux 4.4e-7; E max-pool 4.7e-8 forward, 1.3e-7 backward, sums 1.1e-7 / 1.4e-7; B, C, F through
+test_conv2d_forward_data_and_weight_gradient: forward 3.7e-7, weight gradient 4.4e-7, data gradient 8.8e-7."""
 import functools
 
 import numpy as np
@@ -19,6 +24,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv2d_rect_cases as RC
 from oracle import stgcn as O
 from util import NAN, SENTINEL, Launch, drive, guarded, guarded_flat, mask_bytes, rejected, rel_err, to_cn
 
@@ -709,7 +715,10 @@ def test_projection_graph_convolution(dev, pad):
 # (cin, cout, k, stride, H, W): the smallest shapes of tests/test_gpu_conv2d_kernels.py, the stem at H = 32, and two rectangular images
 # (every other fp32 2-D test is square: an H / W exchange in the geometry would pass them)
 C2D_SHAPES = [(8, 8, 3, 1, 16, 16), (24, 40, 3, 1, 20, 20), (16, 32, 3, 2, 64, 64), (1, 64, 7, 2, 32, 32), (8, 8, 3, 1, 12, 20),
-              (16, 32, 3, 2, 12, 20)]
+              (16, 32, 3, 2, 12, 20),
+              # one case each of groups B, C and F of tests/conv2d_rect_cases.py: 1x1 / stride 2 onto 7 x 9, the stem at 25 x 35, the
+              # fixed-geometry weight gradient v3 with a ragged last row tile (H_out = 11, th = 8)
+              (8, 16, 1, 2, 13, 18), (1, 40, 7, 2, 25, 35), (24, 40, 3, 1, 11, 16)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -808,6 +817,33 @@ def test_conv2d_stride2_data_gradient_parity_classes(dev, cin, cout, H, pad):
     drive(dev, fn, pad)
 
 
+@pytest.mark.parametrize("pad", PADS)
+@pytest.mark.parametrize("cin,cout,H,W", RC.A_PARITY + RC.A_MASKED)
+def test_conv2d_stride2_data_gradient_rectangular(dev, cin, cout, H, W, pad):
+    """group A of tests/conv2d_rect_cases.py: H x W images, both sides even (parity classes, with the compact aux) or not (masked kernel)"""
+    from sar_amd import ops, _lib as L
+    B = RC.A_BATCH
+    c = RC.conv_ref(cin, cout, 3, 2, H, W, B)
+    Ho, Wo = c["Ho"], c["Wo"]
+    wb = c["w"].permute(2, 3, 0, 1).reshape(-1).contiguous().to(dev)          # (tap, m, c)
+    geo = dict(B=B, Kc=cout, M=cin, H_src=Ho, W_src=Wo, H_out=H, W_out=W, KH=3, KW=3, stride=2, pad=1, transposed=True)
+
+    def fn(g):
+        dyd = g.inp(cn(c["dy"]))
+        dx = g.out("dx", cin, B * H * W)
+        r = ops.conv2d_gemm(dyd, dx, wb, cout * cin, cin, epi=L.SAR_EPI_MASK, aux=g.inp(c["aux"]),
+                            aux_affine=(c["sc2"].to(dev), c["sh2"].to(dev)), aux_mean=c["mu"].to(dev), **geo)
+        g.part("mask", r[0])
+        g.ref("masked data gradient", dx, c["dz"], TOL)
+        g.ref("sum dz", lambda: r[0].double().sum(1)[:, 0], c["dz_sum"], 1e-4)
+        g.ref("sum dz (aux - mean)", lambda: r[0].double().sum(1)[:, 1], c["dz_cen"], 1e-4)
+        if RC.dgrad_s2_route(H, W) == "parity":
+            dx2 = g.out("dx + even pixels", cin, B * H * W)
+            ops.conv2d_gemm(dyd, dx2, wb, cout * cin, cin, epi=L.SAR_EPI_ADD, aux=g.inp(c["small"]), aux_even_pixels=True, **geo)
+            g.ref("data gradient + compact aux", dx2, cn(c["gh_even"]), TOL)
+    drive(dev, fn, pad)
+
+
 @functools.lru_cache(maxsize=None)
 def maxpool_case():
     """tests/test_gpu_conv2d_kernels.py: test_stem_tail_maxpool_forward_backward"""
@@ -840,4 +876,26 @@ def test_bn_relu_maxpool_forward_and_backward(dev, pad):
         g.ref("max-pool backward", dz, cn(gz), TOL)
         g.ref("sum dz", lambda: part.double().sum(1)[:, 0], gz.sum(dim=(0, 2, 3)), 1e-4)
         g.ref("sum dz (x - mean)", lambda: part.double().sum(1)[:, 1], (gz * (x - mean64.view(1, -1, 1, 1))).sum(dim=(0, 2, 3)), 1e-4)
+    drive(dev, fn, pad)
+
+
+@pytest.mark.parametrize("pad", PADS)
+@pytest.mark.parametrize("B,C,H,W", RC.E_CASES)
+def test_bn_relu_maxpool_forward_and_backward_rectangular(dev, B, C, H, W, pad):
+    """group E of tests/conv2d_rect_cases.py: H x W images; (18, 131) and (17, 260) tile the backward 2 x 2 and 2 x 3"""
+    from sar_amd import ops
+    c = RC.maxpool_ref(B, C, H, W)
+    Ho, Wo = c["Ho"], c["Wo"]
+    scd, shd = c["sc"].to(dev), c["sh"].to(dev)
+
+    def fn(g):
+        xd = g.inp(cn(c["x"]))
+        yd, dz = g.out("y", C, B * Ho * Wo), g.out("dz", C, B * H * W)
+        ops.bn_relu_maxpool_fwd(xd, scd, shd, yd, B, H, W)
+        part, _ = ops.bn_relu_maxpool_bwd(xd, scd, shd, c["mean"].float().to(dev), g.inp(cn(c["dy"])), dz, B, H, W)
+        g.part("backward", part)
+        g.ref("max-pool forward", yd, cn(c["y"]), TOL)
+        g.ref("max-pool backward", dz, cn(c["gz"]), TOL)
+        g.ref("sum dz", lambda: part.double().sum(1)[:, 0], c["gz_sum"], 1e-4)
+        g.ref("sum dz (x - mean)", lambda: part.double().sum(1)[:, 1], c["gz_cen"], 1e-4)
     drive(dev, fn, pad)

@@ -1,7 +1,13 @@
 """GPU parity of the spectrogram path's classifier: the HIP ResNet-18 engine (through the C ABI) against
  (1) the golden outputs of the REFERENCE's own models/resnet18.py (tests/golden/resnet18_tiny.npz: 8 filters, 64x64),
  (2) the CPU oracle at the reference's real shape (64 filters, 256x256 images),
-and the drop-in models.resnet.Model / main_spectrogram.py."""
+and the drop-in models.resnet.Model / main_spectrogram.py.
+
+test_rectangular_images_match_the_oracle: the engine on rectangular and odd-sized images (every other test here feeds 64 x 64 or
+256 x 256).  MEASURED on an MI355X, bar 1e-4 (worst gradient / worst of activations, logits, loss, dx, moving statistics, eval):
+  (3, 1, 48, 80)   fp32 4.7e-6 / 3.3e-6    f32_split 4.0e-6 / 2.4e-6
+  (3, 1, 50, 70)   fp32 6.0e-6 / 3.2e-6    f32_split 6.9e-6 / 2.5e-6
+  (2, 1, 64, 40)   fp32 9.7e-6 / 5.0e-6    f32_split 6.1e-6 / 2.8e-6"""
 import os
 import subprocess
 import sys
@@ -48,25 +54,36 @@ def test_tiny_resnet_matches_reference_golden(dev, golden_dir):
     assert rel_err(out.cpu(), torch.from_numpy(gold["logits_eval"])) < 1e-4
 
 
-def _engine_masks(eng, keep, B):
+def _engine_masks(eng, keep, B, hw=None):
     """The engine's activation pattern at every ReLU site, in the oracle's NCHW layout.  Block outputs: y > 0.  The
     ReLUs folded into the conv operand load (stem bn1, every block's bn1) are re-evaluated with the engine's own
-    kernel arithmetic relu(fma(x, scale, shift)) through sar_bn_add_relu_fwd_f32."""
+    kernel arithmetic relu(fma(x, scale, shift)) through sar_bn_add_relu_fwd_f32.  hw: the (H, W) of every site, keyed like the
+    masks -- from the oracle's tap shapes (_tap_sizes); None: square maps, the side length from the element count."""
     from sar_amd import ops
     masks = {}
-    def nchw(t):
+    def nchw(t, site):
         n = t.shape[1] // B
-        h = int(round(n ** 0.5))
-        return (t > 0).cpu().view(t.shape[0], B, h, h).permute(1, 0, 2, 3)
-    def folded(x, bn):
+        h, w = hw[site] if hw is not None else (int(round(n ** 0.5)),) * 2
+        assert h * w == n, (site, h, w, n)
+        return (t > 0).cpu().view(t.shape[0], B, h, w).permute(1, 0, 2, 3)
+    def folded(x, bn, site):
         out = torch.empty_like(x)
         ops.bn_add_relu_fwd(x, bn.scale, bn.shift, 0, None, None, None, out)
-        return nchw(out)
-    masks["bn1"] = folded(keep["conv1"], eng.bn["bn1"])
+        return nchw(out, site)
+    masks["bn1"] = folded(keep["conv1"], eng.bn["bn1"], "bn1")
     for pre, _, _, _, _ in eng.blocks:
-        masks[pre + "bn1"] = folded(keep[pre + "c1"], eng.bn[pre + "bn1"])
-        masks[pre + "out"] = nchw(keep[pre + "out"])
+        masks[pre + "bn1"] = folded(keep[pre + "c1"], eng.bn[pre + "bn1"], pre + "bn1")
+        masks[pre + "out"] = nchw(keep[pre + "out"], pre + "out")
     return masks
+
+
+def _tap_sizes(eng, taps):
+    """(H, W) of every ReLU site from the oracle's taps: the stem's bn1 acts on conv1's output, a block's bn1 on a map of the size of
+    that block's output"""
+    hw = {"bn1": tuple(taps["conv1"].shape[2:])}
+    for pre, _, _, _, _ in eng.blocks:
+        hw[pre + "bn1"] = hw[pre + "out"] = tuple(taps[pre + "out"].shape[2:])
+    return hw
 
 
 def test_full_width_resnet_matches_oracle(dev):
@@ -206,6 +223,71 @@ def test_image_gradient_of_the_stem(dev):
     torch.nn.functional.cross_entropy(lo, y).backward()
     assert dx.shape == x.shape
     assert rel_err(dx.cpu(), xr.grad) < 1e-4
+
+
+# (B, H, W): 48 x 80 -> stem tail at 24 x 40, stride-2 data gradients onto 12 x 20 and 6 x 10 (parity classes) and 3 x 5 (masked);
+# 50 x 70 -> tail at 25 x 35, 13 x 18 / 7 x 9 / 4 x 5: the masked kernel at every stage; 64 x 40 (H the long side) -> tail at 32 x 20,
+# 16 x 10 (parity classes), 8 x 5 (H even, W odd: masked) and 4 x 3 (masked)
+RECT_IMAGES = [(3, 48, 80), (3, 50, 70), (2, 64, 40)]
+
+
+@pytest.mark.parametrize("B,H,W", RECT_IMAGES)
+def test_rectangular_images_match_the_oracle(dev, B, H, W):
+    """ResNet18(num_classes=5, num_filters=8) with randomised BatchNorm affine parameters on rectangular and odd-sized images against
+    oracle/resnet.py in float64, conditioned on the engine's activation pattern as in test_full_width_resnet_matches_oracle: conv1,
+    pool and every block output, logits, loss, every gradient, d loss / d image, the moving statistics and the eval-mode forward,
+    each under 1e-4; and a second loss_and_grad on the same state repeats logits, loss and the gradient buffer bit for bit."""
+    from sar_amd.resnet import ResNet18
+    eng = ResNet18(num_classes=5, num_filters=8, device=dev, seed=H)
+    p = {k: v.double() for k, v in eng.state_dict().items()}
+    g = torch.Generator().manual_seed(H + W)
+    for name, c in eng.bn_names:
+        p[name + ".weight"] = (1 + 0.2 * torch.randn(c, generator=g)).double()
+        p[name + ".bias"] = (0.2 * torch.randn(c, generator=g)).double()
+    x = torch.randn((B, 1, H, W), generator=g)
+    y = torch.randint(0, 5, (B,), generator=g)
+    lref, loss_ref, _, stats, taps = RN.loss_and_grads(p, x.double(), y)
+    eng.load_params(p)
+    keep = {}
+    logits = eng.forward(x.to(dev), training=True, keep=keep)
+    torch.cuda.synchronize()
+    def nchw(t, like):
+        return t.cpu().view(like.shape[1], B, like.shape[2], like.shape[3]).permute(1, 0, 2, 3)
+    errs = {k: rel_err(nchw(keep[k], taps[k]), taps[k]) for k in ["conv1", "pool"] + [blk[0] + "out" for blk in eng.blocks]}
+    errs["logits"] = rel_err(logits.cpu(), lref)
+    masks = _engine_masks(eng, keep, B, _tap_sizes(eng, taps))
+    # the oracle conditioned on the engine's pattern, with the image a leaf
+    names = RN.trainable(p)
+    q = dict(p)
+    q.update({k: p[k].clone().requires_grad_(True) for k in names})
+    xr = x.double().requires_grad_(True)
+    lo = RN.forward(q, xr, True, {}, {}, masks=masks)
+    grads = torch.autograd.grad(torch.nn.functional.cross_entropy(lo, y), [xr] + [q[k] for k in names])
+    eng.load_params(p)                      # restore the moving statistics touched by the first forward
+    logits, loss, dx = eng.loss_and_grad(x.to(dev), y.to(dev), need_dx=True)
+    torch.cuda.synchronize()
+    first = (logits.clone(), loss.clone(), eng.grad.clone())
+    errs["loss"] = rel_err(loss.cpu(), loss_ref.reshape(1))
+    errs["logits (step)"] = rel_err(logits.cpu(), lref)
+    errs["dx"] = rel_err(dx.cpu(), grads[0])
+    gerr = {k: rel_err(eng.g[k].cpu(), gk) for k, gk in zip(names, grads[1:])}
+    for name, b in eng.bn.items():
+        errs[name + ".running_mean"] = rel_err(b.moving_mean.cpu(), stats[name + ".running_mean"])
+        errs[name + ".running_var"] = rel_err(b.moving_var.cpu(), stats[name + ".running_var"])
+    after = dict(p)
+    after.update(stats)
+    out = eng.forward(x.to(dev), training=False)
+    torch.cuda.synchronize()
+    errs["logits (eval)"] = rel_err(out.cpu(), RN.forward(after, x.double(), False))
+    worst = lambda d: sorted(d.items(), key=lambda kv: -kv[1])[:4]
+    print("RECT engine %dx%d: worst gradients %s; worst of the rest %s" % (H, W, worst(gerr), worst(errs)))
+    bad = {k: v for k, v in list(errs.items()) + list(gerr.items()) if not v < 1e-4}
+    assert not bad, bad
+    assert dx.shape == x.shape and set(gerr) == set(eng.shapes)
+    eng.load_params(p)
+    logits, loss = eng.loss_and_grad(x.to(dev), y.to(dev))
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(first, (logits, loss, eng.grad)))
 
 
 def test_spectrogram_train_step_is_bitwise_deterministic(dev):
