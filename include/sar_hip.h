@@ -1066,6 +1066,36 @@ int sar_tattn_dx_f32(const float* dout, int64_t d_sn, int64_t d_sc, const float*
                      int N, int C, int T, int V, int units, float* dx, int64_t g_sn, int64_t g_sc, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * AdaptiveAdjacency: the data-dependent adjacency term C_k of 2s-AGCN (no reference counterpart; the producer of the per-sample
+ * adjacency SGCN consumes).  csrc/adjattn.hip, fp32; both products run on v_mfma_f32_32x32x2_f32.
+ * theta, phi and their gradients: CN matrices [K*Ce][ld] with columns (n, t, v), ld >= N*T*V; channel k*Ce + e belongs to subset k.
+ * S, P, A_eff, dA_eff, dS: contiguous (N, K, V, V); A, dA: contiguous (K, V, V).
+ *   S[n,k,v,w] = (1 / (Ce*T)) sum_{e,t} theta[k*Ce + e][n,t,v] phi[k*Ce + e][n,t,w]
+ *   P[n,k,:,w] = softmax over v of S[n,k,:,w] (every column sums to 1);  A_eff = A[k] + P
+ * Limits (SAR_E_ARG / SAR_E_UNSUP before any launch): 1 <= V <= SAR_ADJATTN_VMAX, 1 <= K <= SAR_ADJATTN_KMAX,
+ * 1 <= K*Ce <= SAR_ADJATTN_EMAX, N*T*V < 2^22, N*K <= 65535, N*T*V <= ld < 2^31; no output may be an input.  No atomics: repeated
+ * launches are bitwise equal, and a sample's results depend on the sample's data only.
+ *   sar_adjattn_sim_f32          S.  The contraction of length Ce*T is cut into nslab = sar_adjattn_sim_slabs(Ce, T, V) runs (a function
+ *                                of the shape alone) and each run into four; partials are added in a fixed order in fp64.  slab:
+ *                                nslab * N*K*V*V floats of workspace, may be NULL when nslab = 1
+ *   sar_adjattn_softmax_f32      P and A_eff from S and A (the column maximum is subtracted; expf)
+ *   sar_adjattn_softmax_bwd_f32  dS = P (dA_eff - g), g[n,k,w] = sum_v P dA_eff; with dA != NULL also dA[k] = sum_n dA_eff[n,k], in
+ *                                sample order in fp64
+ *   sar_adjattn_dembed_f32       dtheta[k*Ce + e][n,t,v] = (1 / (Ce*T)) sum_w dS[n,k,v,w] phi[k*Ce + e][n,t,w] and
+ *                                dphi[k*Ce + e][n,t,w] = (1 / (Ce*T)) sum_v dS[n,k,v,w] theta[k*Ce + e][n,t,v], [K*Ce][ld_d] each, one
+ *                                launch, every live element written once */
+#define SAR_ADJATTN_VMAX 32
+#define SAR_ADJATTN_KMAX 4
+#define SAR_ADJATTN_EMAX 512
+int sar_adjattn_sim_slabs(int Ce, int T, int V);
+int sar_adjattn_sim_f32(const float* theta, const float* phi, int64_t ld, int N, int K, int Ce, int T, int V, float* S, float* slab,
+                        int nslab, sar_stream_t s);
+int sar_adjattn_softmax_f32(const float* S, const float* A, int N, int K, int V, float* P, float* A_eff, sar_stream_t s);
+int sar_adjattn_softmax_bwd_f32(const float* P, const float* dA_eff, int N, int K, int V, float* dS, float* dA, sar_stream_t s);
+int sar_adjattn_dembed_f32(const float* dS, const float* theta, const float* phi, int64_t ld, int N, int K, int Ce, int T, int V,
+                           float* dtheta, float* dphi, int64_t ld_d, sar_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------
  * Box calibration (csrc/box_probe.hip; bench.py's "box" object -- no reference counterpart, measurement only): what the box
  * this process landed on sustains, so that a line's `frac` (against the guide's peaks) can be read next to `frac_of_box`.
  *   sar_box_mfma        dense loop of one matrix instruction: kind 0 = v_mfma_f32_32x32x2_f32, 1 = v_mfma_f32_32x32x16_f16,

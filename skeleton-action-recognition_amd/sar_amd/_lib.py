@@ -254,6 +254,12 @@ SIGNATURES = {
     "sar_tattn_wgrad_slabs": (_i, [_i, _i, _i, _i]),
     "sar_tattn_wgrad_f32": (_i, [_fp, _i64, _i64, _fp, _i64, _i, _i, _i, _i, _i, _fp, _i, _fp]),
     "sar_tattn_dx_f32": (_i, [_fp, _i64, _i64, _fp, _fp, _fp, _i64, _i, _i, _i, _i, _i, _fp, _i64, _i64, _fp]),
+    # AdaptiveAdjacency: the similarity of the two embeddings, its column softmax, their gradients (csrc/adjattn.hip)
+    "sar_adjattn_sim_slabs": (_i, [_i, _i, _i]),
+    "sar_adjattn_sim_f32": (_i, [_fp, _fp, _i64, _i, _i, _i, _i, _i, _fp, _fp, _i, _fp]),
+    "sar_adjattn_softmax_f32": (_i, [_fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
+    "sar_adjattn_softmax_bwd_f32": (_i, [_fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
+    "sar_adjattn_dembed_f32": (_i, [_fp, _fp, _fp, _i64, _i, _i, _i, _i, _i, _fp, _fp, _i64, _fp]),
     # box calibration (bench.py "box"; csrc/box_probe.hip)
     "sar_box_mfma": (_i, [_i, _i, _i, _fp, _fp, _fp]),
     "sar_box_mfma_flops": (_i64, [_i, _i, _i]),

@@ -1466,6 +1466,101 @@ def tattn_backward(x, saved, params, dout, need_dx=True, dx=None, keep=None):
     return dx, grads
 
 
+# ------------------------------------------------------------------------------------------------ AdaptiveAdjacency
+# csrc/adjattn.hip (include/sar_hip.h: AdaptiveAdjacency).  X / dX: CN matrices [C][ld] with columns (n, t, v) -- the modules' to_cn(x)
+# or an engine's own matrix (a row-strided view with N T V live columns); A (K, V, V); the kernels in the Keras layout (1, 1, C, K Ce)
+# (or (C, K Ce)), channel k Ce + e of subset k; phi_bias (K Ce).  theta and phi are ONE 1x1 product on the stacked kernel [C][2 K Ce]
+# (theta's columns, then phi's; zeros in the bias of theta's half) per pass, through the helpers every layer of models/gcn.py uses.
+ADJATTN_VMAX, ADJATTN_KMAX, ADJATTN_EMAX = 32, 4, 512
+
+
+def _adjattn_check(X, N, T, V, A, theta_kernel, phi_kernel, phi_bias=None, dense=()):
+    """ValueError before the library is touched -> (C, K, Ce)"""
+    ts = [X, A, theta_kernel, phi_kernel] + ([phi_bias] if phi_bias is not None else []) + list(dense)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("AdaptiveAdjacency operands must be tensors")
+    if min(N, T, V) < 1 or not (X.dim() == 2 and X.shape[0] >= 1 and X.shape[1] == N * T * V and X.stride(1) == 1 and X.stride(0) >= X.shape[1]):
+        raise ValueError("X must be a CN matrix [C][N T V = %d columns], contiguous or a row-strided view with a unit column stride (got "
+                         "shape %s, strides %s)" % (N * T * V, tuple(X.shape), tuple(X.stride())))
+    C = X.shape[0]
+    if not (A.dim() == 3 and tuple(A.shape[1:]) == (V, V)):
+        raise ValueError("A must be (K, V, V) = (K, %d, %d), got %s" % (V, V, tuple(A.shape)))
+    K = A.shape[0]
+    if not (1 <= V <= ADJATTN_VMAX and 1 <= K <= ADJATTN_KMAX):
+        raise ValueError("AdaptiveAdjacency is built for 1 <= V <= %d and 1 <= K <= %d (got V = %d, K = %d)" % (ADJATTN_VMAX, ADJATTN_KMAX, V, K))
+    kce = theta_kernel.shape[-1] if theta_kernel.dim() >= 2 else 0
+    for name, kernel in (("theta_kernel", theta_kernel), ("phi_kernel", phi_kernel)):
+        if not (kernel.dim() in (2, 4) and kernel.numel() == C * kce and tuple(kernel.shape[-2:]) == (C, kce)):
+            raise ValueError("%s must be (1, 1, C, K Ce) = (1, 1, %d, %d), got %s" % (name, C, kce, tuple(kernel.shape)))
+    if not (1 <= kce <= ADJATTN_EMAX and kce % K == 0):
+        raise ValueError("AdaptiveAdjacency is built for 1 <= K Ce <= %d, a multiple of K = %d (got %d)" % (ADJATTN_EMAX, K, kce))
+    if phi_bias is not None and tuple(phi_bias.shape) != (kce,):
+        raise ValueError("phi_bias must be (K Ce) = (%d), got %s" % (kce, tuple(phi_bias.shape)))
+    if N * T * V >= 1 << 22 or N * K > 65535:
+        raise ValueError("AdaptiveAdjacency is built for N T V < 2^22 columns (the 1x1 product) and N K <= 65535 (got N = %d, T = %d, V = %d, "
+                         "K = %d)" % (N, T, V, K))
+    for t in ts[1:]:
+        if not t.is_contiguous():
+            raise ValueError("a parameter or per-sample operand must be contiguous (got shape %s, strides %s)" % (tuple(t.shape), tuple(t.stride())))
+    for t in ts:
+        if not (t.is_cuda and t.dtype == torch.float32):
+            raise ValueError("AdaptiveAdjacency operands must be float32 CUDA tensors (got %s on %s)" % (t.dtype, t.device))
+    return C, K, kce // K
+
+
+def _adjattn_stacked(theta_kernel, phi_kernel, C):
+    return torch.cat([theta_kernel.reshape(C, -1), phi_kernel.reshape(C, -1)], dim=1)
+
+
+def adjattn_forward(X, N, T, V, A, theta_kernel, phi_kernel, phi_bias, keep=None):
+    """A_eff[n, k] = A[k] + softmax_v(theta_k(x_n)^T phi_k(x_n) / (Ce T)) of the CN matrix X [C][ld].  Returns (A_eff (N, K, V, V), saved):
+    saved = (E [2 K Ce][N T V]: theta's rows, then phi's; P (N, K, V, V)) is what adjattn_backward needs besides X and the kernels.
+    keep: a dict that receives the logits "S" (N, K, V, V), for the tests."""
+    C, K, Ce = _adjattn_check(X, N, T, V, A, theta_kernel, phi_kernel, phi_bias)
+    from models.gcn import _conv1x1_fwd       # (models.gcn imports this module: the helpers are looked up at the call)
+    dev, kce = X.device, K * Ce
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    lib, st = L.load(), stream_ptr()
+    bias = torch.cat([torch.zeros(kce, dtype=torch.float32, device=dev), phi_bias])
+    E = _conv1x1_fwd(X, _adjattn_stacked(theta_kernel, phi_kernel, C), bias, dict(B=N, V=V, T_src=T, T_out=T))
+    S, P, A_eff = new(N, K, V, V), new(N, K, V, V), new(N, K, V, V)
+    nslab = lib.sar_adjattn_sim_slabs(Ce, T, V)
+    slab = new(nslab, N * K * V * V) if nslab > 1 else None
+    check(lib.sar_adjattn_sim_f32(ptr(E), ptr(E[kce:]), E.stride(0), N, K, Ce, T, V, ptr(S), ptr(slab), nslab, st), "sar_adjattn_sim_f32")
+    check(lib.sar_adjattn_softmax_f32(ptr(S), ptr(A), N, K, V, ptr(P), ptr(A_eff), st), "sar_adjattn_softmax_f32")
+    if keep is not None:
+        keep["S"] = S
+    return A_eff, (E, P)
+
+
+def adjattn_backward(X, N, T, V, saved, theta_kernel, phi_kernel, dA_eff, need_dx=True, need_dA=True, keep=None):
+    """Backward of adjattn_forward from dA_eff (N, K, V, V).  Returns (dX [C][N T V] | None, dtheta_kernel, dphi_kernel, dphi_bias,
+    dA (K, V, V) | None); without need_dx the input gradient's product is not launched, without need_dA the sum over the samples is not.
+    keep: a dict that receives "dS" (N, K, V, V) and "dE" [2 K Ce][N T V] (dtheta's rows, then dphi's), for the tests."""
+    E, P = saved
+    if not (isinstance(P, torch.Tensor) and P.dim() == 4 and isinstance(dA_eff, torch.Tensor) and tuple(dA_eff.shape) == tuple(P.shape)):
+        raise ValueError("dA_eff must have the shape of the saved P, (N, K, V, V)")
+    if not (isinstance(E, torch.Tensor) and isinstance(theta_kernel, torch.Tensor) and theta_kernel.dim() >= 2 and P.shape[0] == N
+            and tuple(E.shape) == (2 * theta_kernel.shape[-1], N * T * V)):
+        raise ValueError("saved does not belong to these kernels and this X")
+    C, K, Ce = _adjattn_check(X, N, T, V, P[0], theta_kernel, phi_kernel, dense=(E, P, dA_eff))
+    kce, n = K * Ce, N * T * V
+    from models.gcn import _conv1x1_dgrad, _conv1x1_wgrad
+    dev = X.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    lib, st, geo = L.load(), stream_ptr(), dict(B=N, V=V, T_src=T, T_out=T)
+    dS, dA, dE = new(N, K, V, V), (new(K, V, V) if need_dA else None), new(2 * kce, n)
+    check(lib.sar_adjattn_softmax_bwd_f32(ptr(P), ptr(dA_eff), N, K, V, ptr(dS), ptr(dA), st), "sar_adjattn_softmax_bwd_f32")
+    check(lib.sar_adjattn_dembed_f32(ptr(dS), ptr(E), ptr(E[kce:]), n, N, K, Ce, T, V, ptr(dE), ptr(dE[kce:]), n, st), "sar_adjattn_dembed_f32")
+    if keep is not None:
+        keep["dS"], keep["dE"] = dS, dE
+    dW, db = _conv1x1_wgrad(X, dE, geo)
+    dW = dW.view(C, 2 * kce)
+    dtk, dpk = dW[:, :kce].contiguous().view(theta_kernel.shape), dW[:, kce:].contiguous().view(phi_kernel.shape)
+    dX = _conv1x1_dgrad(dE, _adjattn_stacked(theta_kernel, phi_kernel, C), geo) if need_dx else None
+    return dX, dtk, dpk, db[kce:], dA
+
+
 # ------------------------------------------------------------------------------------------------ ResNet-18 ops
 def _shape_tag(geo):
     """SAR_PROFILE_SHAPES=1 (diagnostic, tools/pathb_layers.py): one profiler bucket per layer geometry"""
