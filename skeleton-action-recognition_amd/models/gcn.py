@@ -13,7 +13,7 @@ the default einsum string of each layer is implemented; any other raises ValueEr
 
 Each layer call is ONE torch.autograd.Function over sar_amd.ops:
   * the 1x1 convolution is sar_conv_gemm_f32 (TEMPORAL, taps = 1) with its weight / data gradients, written once for every layer
-    of this file: _conv1x1_fwd / _conv1x1_wgrad / _conv1x1_dgrad;
+    of this package and every layer wrapper: ops.conv1x1_fwd / conv1x1_wgrad / conv1x1_dgrad over ops.column_geometry;
   * _ConvContractFn is the 1x1 product followed by a contraction with A, parameterised by the contraction's three kernels:
     GraphConv contracts with the per-sample adjacency on csrc/graph_sample.hip (V <= 512);
   * GraphConvTD takes the fused gather-list kernel (_GraphConvTDFusedFn: sar_conv_gemm_f32 GRAPH with GraphTables, exactly as the
@@ -90,43 +90,6 @@ def variance_scaling_(kernel):
         kernel.copy_(w.to(torch.float32))
 
 
-# ---- the 1x1 convolution shared by every layer: columns (B, T, V) of a CN matrix, V <= 64 (sar_conv_gemm_f32's limit); fp32 whatever
-# SAR_* split arithmetic is set (split=None).  `out` = rows of a caller's stacked matrix; **kw goes to the kernel as it is
-def _conv1x1_fwd(X, W, bias, geo, out=None, **kw):
-    """out (M, n) = W^T X + bias; kw: pro, pro_relu (BN + ReLU on the operand load), epi, partials_out (the statistics epilogue)"""
-    C, M = W.shape
-    if out is None:
-        out = torch.empty((M, X.shape[1]), dtype=torch.float32, device=X.device)
-    ops.conv_gemm(L.SAR_CONV_TEMPORAL, X, out, W, 0, M, Kc=C, M=M, taps=1, stride=1, pad=0, bias=bias, split=None, **geo, **kw)
-    return out
-
-
-def _conv1x1_wgrad(X, dy, geo, **kw):
-    """(dW (C M), dbias (M)) of X (C, n) and dy (M, n), one launch; kw: pro, pro_relu"""
-    C, M = X.shape[0], dy.shape[0]
-    flat = torch.empty(C * M + M, dtype=torch.float32, device=X.device)
-    ops.conv_wgrad(L.SAR_CONV_TEMPORAL, X, dy, flat, Kc=C, M=M, taps=1, stride=1, pad=0, w_stride_tap=0, w_stride_c=M, wsize=C * M,
-                   bsize=M, split=None, **geo, **kw)
-    return flat[:C * M], flat[C * M:]
-
-
-def _conv1x1_dgrad(dy, W, geo, out=None, **kw):
-    """out (C, n) = W dy; kw: epi, aux, aux_affine, aux_mean, partials_out (the masked gradient through a folded BN + ReLU)"""
-    C, M = W.shape
-    WT = torch.empty((M, C), dtype=torch.float32, device=dy.device)
-    ops.transpose(W, WT, 1, C, M)
-    if out is None:
-        out = torch.empty((C, dy.shape[1]), dtype=torch.float32, device=dy.device)
-    ops.conv_gemm(L.SAR_CONV_TEMPORAL, dy, out, WT, 0, C, Kc=M, M=C, taps=1, stride=1, pad=0, transposed=True, split=None, **geo, **kw)
-    return out
-
-
-def _column_geometry(N, V):
-    """a (B, T, V') factorisation of the N * V columns with V' <= 64: the 1x1 product does not care which"""
-    vf = max(d for d in range(1, min(V, 64) + 1) if V % d == 0)
-    return dict(B=N, V=vf, T_src=V // vf, T_out=V // vf)
-
-
 # (forward, data gradient, adjacency gradient) of the two contractions behind a 1x1 product, each called as op(in, A, out, *dims)
 # (the adjacency gradient as op(y, dout, dA, *dims))
 SAMPLE_CONTRACTION = (ops.graph_sample_fwd, ops.graph_sample_bwd_data, ops.graph_sample_dA)      # dims (F, V, N): A (N, V, V), V <= 512
@@ -143,7 +106,7 @@ class _ConvContractFn(torch.autograd.Function):
         C = x.shape[1]
         to_cn, from_cn = columns
         X = to_cn(x)
-        y = _conv1x1_fwd(X, kernel.view(C, -1), bias, geo)
+        y = ops.conv1x1_fwd(X, kernel.view(C, -1), bias, geo)
         out = torch.empty((F, X.shape[1]), dtype=torch.float32, device=x.device)
         contraction[0](y, A, out, *dims)
         ctx.save_for_backward(X, y, A, kernel)
@@ -167,10 +130,10 @@ class _ConvContractFn(torch.autograd.Function):
             bwd_data(dc, A, dy, *ctx.dims)
             W = kernel.view(C, -1)
             if need_k or need_b:
-                dW, db = _conv1x1_wgrad(X, dy, ctx.geo)
+                dW, db = ops.conv1x1_wgrad(X, dy, ctx.geo)
                 dW = dW.view(kernel.shape)
             if need_x:
-                dx = from_cn(_conv1x1_dgrad(dy, W, ctx.geo), ctx.shape)
+                dx = from_cn(ops.conv1x1_dgrad(dy, W, ctx.geo), ctx.shape)
         return dx, dA, dW, db, None, None, None, None, None
 
 
@@ -273,7 +236,7 @@ class GraphConv(_Conv1x1Layer):
             raise ValueError("N * V = %d columns: the 1x1 product is built for fewer than 2^22" % (N * V))
         self.build(C, x.device)
         return _ConvContractFn.apply(x, A, self.kernel, self.bias, SAMPLE_CONTRACTION, (self.out_channels, V, N), self.out_channels,
-                                     _column_geometry(N, V)), A
+                                     ops.column_geometry(N, V)), A
 
 
 def _dense_limits(K, V):
@@ -426,7 +389,7 @@ def _mlp_forward(src, branches, geo, n, training, unbiased):
             kw = dict(pro=(_rows(prev.scale, k, cin), _rows(prev.shift, k, cin)), pro_relu=True) if prev is not None else {}
             if stats:
                 kw.update(epi=L.SAR_EPI_STATS, partials_out=_rows(part, k, f))
-            _conv1x1_fwd(_rows(src, k, cin), l.kernel.view(cin, f), l.bias, geo, out=_rows(a, k, f), **kw)
+            ops.conv1x1_fwd(_rows(src, k, cin), l.kernel.view(cin, f), l.bias, geo, out=_rows(a, k, f), **kw)
             if l.has_bn:
                 _bn_forward(st, k, (_rows(part, k, f), nparts) if stats else None, n, l, training, unbiased)
         saved.acts.append(a), saved.states.append(st)
@@ -469,12 +432,12 @@ def _mlp_backward(saved, params, da):
         for k in range(K):
             j, s_k, da_k = at(k, i), _rows(src, k, cin), _rows(da, k, f)
             pro = (_rows(pst.scale, k, cin), _rows(pst.shift, k, cin)) if i else None
-            dW, grads[j + 1] = _conv1x1_wgrad(s_k, da_k, geo, pro=pro, pro_relu=pro is not None)
+            dW, grads[j + 1] = ops.conv1x1_wgrad(s_k, da_k, geo, pro=pro, pro_relu=pro is not None)
             grads[j] = dW.view(params[j].shape)
             # through the hidden BN + ReLU: masked data gradient + BatchNorm-backward sums
             mask = dict(epi=L.SAR_EPI_MASK, aux=s_k, aux_affine=pro, aux_mean=_rows(pst.mean, k, cin),
                         partials_out=_rows(pm, k, cin)) if i else {}
-            _conv1x1_dgrad(da_k, params[j].view(cin, f), geo, out=_rows(dsrc, k, cin), **mask)
+            ops.conv1x1_dgrad(da_k, params[j].view(cin, f), geo, out=_rows(dsrc, k, cin), **mask)
             if i:
                 jp = at(k, i - 1)
                 grads[jp + 2], grads[jp + 3] = _bn_backward(pst, k, (_rows(pm, k, cin), npm), n, cin, params[jp + 2])
@@ -495,7 +458,7 @@ class _GraphIsoConvFn(torch.autograd.Function):
         agg = torch.empty_like(X)
         ops.gin_sample_fwd(X, A, eps, agg, C, V, N)
         # Keras' non-fused 3-D path: biased moving variance
-        out, ctx.mlp = _mlp_forward(agg, layer._all_layers(), _column_geometry(N, V), N * V, training, False)
+        out, ctx.mlp = _mlp_forward(agg, layer._all_layers(), ops.column_geometry(N, V), N * V, training, False)
         ctx.save_for_backward(A, eps, *params)
         ctx.training, ctx.X = training, X
         return from_cn(out, (N, out.shape[0], V))

@@ -22,13 +22,13 @@ the Keras defaults: glorot_uniform, orthogonal, zeros with the forget quarter at
 
 The whole call is ONE torch.autograd.Function over sar_amd.ops:
   * sar_lstm_pack_f32 lays x out as the stack's input matrix [V C][T N] with TIME-MAJOR columns t N + n;
-  * per layer, zin = kernel^T X + bias over all T N columns at once is models/gcn.py's 1x1 product (_conv1x1_fwd), and
+  * per layer, zin = kernel^T X + bias over all T N columns at once is the layers' 1x1 product (ops.conv1x1_fwd), and
     sar_lstm_fwd_f32 walks the T steps in one launch (recurrent weights resident on chip);
   * sar_topk_desc_f32, sar_frame_gather_f32;
   * backward: sar_frame_gather_bwd_f32 (dvalues, the scattered dscores, the gather path's dx), then per layer from the top
-    sar_lstm_bwd_f32 (dz), (d kernel, d bias) = _conv1x1_wgrad(X, dz), d recurrent_kernel = sum_t h_{t-1} dz_t^T as the same launch on
+    sar_lstm_bwd_f32 (dz), (d kernel, d bias) = conv1x1_wgrad(X, dz), d recurrent_kernel = sum_t h_{t-1} dz_t^T as the same launch on
     the VIEWS h[:, 0 : (T-1) N] and dz[:, N : T N] (time-major columns: h_{t-1} is h shifted by N columns), dX = kernel dz
-    (_conv1x1_dgrad); the first layer's dX only when x requires a gradient, added into dx by sar_lstm_unpack_add_f32.
+    (conv1x1_dgrad); the first layer's dX only when x requires a gradient, added into dx by sar_lstm_unpack_add_f32.
 Indices carry no gradient.  Under torch.no_grad(), or when nothing requires a gradient, the kernels get NULL save pointers
 (the gates and c are not written).
 
@@ -41,7 +41,7 @@ import math
 
 import torch
 
-from models.gcn import _column_geometry, _conv1x1_dgrad, _conv1x1_fwd, _conv1x1_wgrad, _require
+from models.gcn import _require
 from sar_amd import ops
 
 MAX_UNITS, MAX_T = 128, 2048
@@ -58,14 +58,14 @@ class _TemporalSamplerFn(torch.autograd.Function):
     def forward(ctx, x, top_k, save, *params):
         N, C, T, V = x.shape
         n, dev, nl = T * N, x.device, len(params) // 3
-        geo = _column_geometry(T, N)
+        geo = ops.column_geometry(T, N)
         X = _new(V * C, n, dev)
         ops.lstm_pack(x, X)
         src, layers = X, []
         for i in range(nl):
             kernel, U, bias = params[3 * i:3 * i + 3]
             u = U.shape[0]
-            zin = _conv1x1_fwd(src, kernel, bias, geo)
+            zin = ops.conv1x1_fwd(src, kernel, bias, geo)
             h = _new(u, n, dev)
             gates, c = (_new(4 * u, n, dev), _new(u, n, dev)) if save else (None, None)
             ops.lstm_fwd(zin, U, h, u, N, T, gates, c)
@@ -99,16 +99,16 @@ class _TemporalSamplerFn(torch.autograd.Function):
             u = U.shape[0]
             dz = _new(4 * u, n, dev)
             ops.lstm_bwd(dh, gates, c, U, dz, u, N, T)
-            grads[3 * i], grads[3 * i + 2] = _conv1x1_wgrad(src, dz, ctx.geo)
+            grads[3 * i], grads[3 * i + 2] = ops.conv1x1_wgrad(src, dz, ctx.geo)
             grads[3 * i] = grads[3 * i].view(kernel.shape)
             if T > 1:       # sum_t h_{t-1} dz_t^T: h shifted by one step is h shifted by N columns; the launch's bias output is discarded
-                grads[3 * i + 1] = _conv1x1_wgrad(h[:, :n - N], dz[:, N:], _column_geometry(T - 1, N))[0].view(U.shape)
+                grads[3 * i + 1] = ops.conv1x1_wgrad(h[:, :n - N], dz[:, N:], ops.column_geometry(T - 1, N))[0].view(U.shape)
             else:
                 grads[3 * i + 1] = torch.zeros_like(U)
             if i > 0:
-                dh = _conv1x1_dgrad(dz, kernel, ctx.geo)
+                dh = ops.conv1x1_dgrad(dz, kernel, ctx.geo)
             elif need_x:
-                ops.lstm_unpack_add(_conv1x1_dgrad(dz, kernel, ctx.geo), dx)
+                ops.lstm_unpack_add(ops.conv1x1_dgrad(dz, kernel, ctx.geo), dx)
         return (dx, None, None) + tuple(grads)
 
 

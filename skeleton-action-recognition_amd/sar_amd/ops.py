@@ -9,6 +9,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import operands as O
 from . import profiler
 from ._lib import ConvDesc, WgradDesc, check, ptr, stream_ptr
 
@@ -554,6 +555,44 @@ def conv_wgrad(mode, src, dout, dW_out, *, B, V, T_src, T_out, Kc, M, taps, stri
     _wgrad_slab_done(slabs, slab, nsplit, n, dW_out)
 
 
+# ---- the 1x1 product of every layer (models/ and the layer wrappers below): columns (B, T, V) of a CN matrix, V <= 64
+# (sar_conv_gemm_f32's limit); fp32 whatever SAR_* split arithmetic is set (split=None).  `out` = rows of a caller's stacked matrix;
+# **kw goes to the kernel as it is
+def conv1x1_fwd(X, W, bias, geo, out=None, **kw):
+    """out (M, n) = W^T X + bias; kw: pro, pro_relu (BN + ReLU on the operand load), epi, partials_out (the statistics epilogue)"""
+    Kc, M = W.shape
+    if out is None:
+        out = torch.empty((M, X.shape[1]), dtype=torch.float32, device=X.device)
+    conv_gemm(L.SAR_CONV_TEMPORAL, X, out, W, 0, M, Kc=Kc, M=M, taps=1, stride=1, pad=0, bias=bias, split=None, **geo, **kw)
+    return out
+
+
+def conv1x1_wgrad(X, dy, geo, **kw):
+    """(dW (C M), dbias (M)) of X (C, n) and dy (M, n), one launch; kw: pro, pro_relu"""
+    Kc, M = X.shape[0], dy.shape[0]
+    flat = torch.empty(Kc * M + M, dtype=torch.float32, device=X.device)
+    conv_wgrad(L.SAR_CONV_TEMPORAL, X, dy, flat, Kc=Kc, M=M, taps=1, stride=1, pad=0, w_stride_tap=0, w_stride_c=M, wsize=Kc * M,
+               bsize=M, split=None, **geo, **kw)
+    return flat[:Kc * M], flat[Kc * M:]
+
+
+def conv1x1_dgrad(dy, W, geo, out=None, **kw):
+    """out (C, n) = W dy; kw: epi, aux, aux_affine, aux_mean, partials_out (the masked gradient through a folded BN + ReLU)"""
+    Kc, M = W.shape
+    WT = torch.empty((M, Kc), dtype=torch.float32, device=dy.device)
+    transpose(W, WT, 1, Kc, M)
+    if out is None:
+        out = torch.empty((Kc, dy.shape[1]), dtype=torch.float32, device=dy.device)
+    conv_gemm(L.SAR_CONV_TEMPORAL, dy, out, WT, 0, Kc, Kc=M, M=Kc, taps=1, stride=1, pad=0, transposed=True, split=None, **geo, **kw)
+    return out
+
+
+def column_geometry(N, V):
+    """a (B, T, V') factorisation of the N * V columns with V' <= 64: the 1x1 product does not care which"""
+    vf = max(d for d in range(1, min(V, 64) + 1) if V % d == 0)
+    return dict(B=N, V=vf, T_src=V // vf, T_out=V // vf)
+
+
 def bn_finalize(partials, nparts, C_, count, eps, momentum, unbiased_running, gamma, beta, running_mean, running_var,
                 mean, rstd, scale, shift, pivot=None):
     """pivot: the per-channel float32 value the producer subtracted before it summed (data_bn_stats), or None"""
@@ -1052,35 +1091,39 @@ def gin_eps_grad_bn(gamma, dgamma, rstd, bn_eps, eps, deps):
                                            ptr(deps), stream_ptr()), "sar_gin_eps_grad_bn_f32")
 
 
+# ================================================================================================ the layer wrappers
+# Every wrapper below checks its operands with sar_amd/operands.py (O.on_gpu, O.cn_matrix, O.dense, O.view4) before L.load() is
+# reached, allocates with _new and takes its 1x1 products from conv1x1_fwd / conv1x1_wgrad / conv1x1_dgrad above; only the size
+# limits of its kernels are its own ("The layer wrappers")
+def _new(dev, dtype=torch.float32):
+    """shape -> an uninitialised tensor on `dev`"""
+    return lambda *shape: torch.empty(shape, dtype=dtype, device=dev)
+
+
 # ------------------------------------------------------------------------------------------------ ST-PGCN projection graph convolution
 # csrc/pgc.hip (include/sar_hip.h: ProjectionGraphConv).  x / out / dout / dx: CN [64][B*P]; q: [32][B*P]
 PGC_C, PGC_J = 64, 32
 PGC_FWD_PART, PGC_DH_PART, PGC_BWD_PART, PGC_SAVED, PGC_DSAVED, PGC_SLAB = 2080, 2048, 4096, 11360, 2080, 8256
 
 
-def _pgc_args(x, B, P):
-    """the row stride of a CN operand [64][B*P]; ValueError before the library is touched for sizes below 1, an operand that is no
-    float32 CUDA tensor, and one that is not 2-D with 64 rows, B * P columns of unit stride and a row stride >= B * P"""
+def _pgc_lds(B, P, **cn):
+    """the row strides of the CN operands [64][B*P], each checked in turn as a float32 CUDA tensor, then as that matrix"""
     if B < 1 or P < 1:
         raise ValueError("ProjectionGraphConv needs B >= 1 and P >= 1 (got B = %d, P = %d)" % (B, P))
-    if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.is_cuda):
-        raise ValueError("operands must be float32 CUDA tensors (got %s)" % (("%s on %s" % (x.dtype, x.device)) if torch.is_tensor(x)
-                                                                             else type(x).__name__))
-    if not (x.dim() == 2 and x.shape[0] == PGC_C and x.shape[1] == B * P and x.stride(1) == 1 and x.stride(0) >= B * P):
-        raise ValueError("a CN operand must be a 2-D tensor of %d rows and B * P = %d columns, contiguous or a row-strided view with a "
-                         "unit column stride (got shape %s, strides %s)" % (PGC_C, B * P, tuple(x.shape), tuple(x.stride())))
-    return x.stride(0)
+    lds = []
+    for what, t in cn.items():
+        O.on_gpu("ProjectionGraphConv", (t,))
+        lds.append(O.cn_matrix(t, PGC_C, B * P, what))
+    return lds
 
 
 def pgc_forward(x, B, P, centers, variance, W, bias, out):
     """out = x + the projection graph convolution of x (models/stpgcn.py:23-47).  Returns (q [32][B*P], saved [B][PGC_SAVED]):
     what the backward pass needs (saved: S | zp | zn | g | h | A | qs | sum_j zp^2 per sample)."""
-    ld, ld_out = _pgc_args(x, B, P), _pgc_args(out, B, P)
-    lib, dev = L.load(), x.device
+    ld, ld_out = _pgc_lds(B, P, x=x, out=out)
+    lib, new = L.load(), _new(x.device)
     G = lib.sar_pgc_nparts(P)
-    q = torch.empty((PGC_J, B * P), dtype=torch.float32, device=dev)
-    part = torch.empty((B, G, PGC_FWD_PART), dtype=torch.float32, device=dev)
-    saved = torch.empty((B, PGC_SAVED), dtype=torch.float32, device=dev)
+    q, part, saved = new(PGC_J, B * P), new(B, G, PGC_FWD_PART), new(B, PGC_SAVED)
     check(lib.sar_pgc_assign_f32(ptr(x), ld, B, P, ptr(_f32(centers)), ptr(_f32(variance)), ptr(q), ptr(part), stream_ptr()),
           "sar_pgc_assign_f32")
     check(lib.sar_pgc_small_fwd_f32(ptr(part), B, G, ptr(centers), ptr(variance), ptr(_f32(W)), ptr(_f32(bias)), ptr(saved),
@@ -1093,23 +1136,22 @@ def pgc_forward(x, B, P, centers, variance, W, bias, out):
 def pgc_backward(x, dout, q, saved, B, P, centers, variance, W, dx, g_centers, g_variance, g_kernel_bias):
     """dx = the gradient w.r.t. x; g_centers / g_variance ([64][32]) and g_kernel_bias (the Conv1D kernel [64*64] followed by its
     bias [64], one contiguous range) are written, not accumulated.  Every sum runs in a fixed order."""
-    ld, ld_dout, ld_dx = _pgc_args(x, B, P), _pgc_args(dout, B, P), _pgc_args(dx, B, P)
+    ld, ld_dout, ld_dx = _pgc_lds(B, P, x=x, dout=dout, dx=dx)
     if not (g_kernel_bias.is_contiguous() and g_kernel_bias.numel() == PGC_C * PGC_C + PGC_C):
         raise ValueError("g_kernel_bias must be one contiguous range of %d elements (got shape %s, strides %s)"
                          % (PGC_C * PGC_C + PGC_C, tuple(g_kernel_bias.shape), tuple(g_kernel_bias.stride())))
-    lib, dev = L.load(), x.device
+    lib, new = L.load(), _new(x.device)
     G = lib.sar_pgc_nparts(P)
-    part = torch.empty((B, G, PGC_DH_PART), dtype=torch.float32, device=dev)
+    part = new(B, G, PGC_DH_PART)
     check(lib.sar_pgc_bwd_reduce_f32(ptr(dout), ld_dout, ptr(q), B, P, ptr(part), stream_ptr()), "sar_pgc_bwd_reduce_f32")
-    dsaved = torch.empty((B, PGC_DSAVED), dtype=torch.float32, device=dev)
-    slab = torch.empty((B, PGC_SLAB), dtype=torch.float32, device=dev)
+    dsaved, slab = new(B, PGC_DSAVED), new(B, PGC_SLAB)
     check(lib.sar_pgc_small_bwd_f32(ptr(part), B, G, ptr(_f32(variance)), ptr(_f32(W)), ptr(saved), ptr(dsaved), ptr(slab), stream_ptr()),
           "sar_pgc_small_bwd_f32")
-    cpart = torch.empty((B, G, PGC_BWD_PART), dtype=torch.float32, device=dev)
+    cpart = new(B, G, PGC_BWD_PART)
     check(lib.sar_pgc_bwd_column_f32(ptr(x), ld, ptr(dout), ld_dout, ptr(q), ptr(saved), ptr(dsaved), ptr(_f32(centers)),
                                      ptr(variance), B, P, ptr(dx), ld_dx, ptr(cpart), stream_ptr()), "sar_pgc_bwd_column_f32")
     nwb = PGC_C * PGC_C + PGC_C
-    sums = torch.empty(2 * PGC_BWD_PART, dtype=torch.float32, device=dev)      # column partials | pooled slabs
+    sums = new(2 * PGC_BWD_PART)      # column partials | pooled slabs
     check(lib.sar_slab_reduce_f32(ptr(slab), B, PGC_SLAB, nwb, ptr(g_kernel_bias), stream_ptr()), "sar_slab_reduce_f32")
     check(lib.sar_slab_reduce_f32(ptr(slab) + 4 * nwb, B, PGC_SLAB, PGC_BWD_PART, ptr(sums) + 4 * PGC_BWD_PART, stream_ptr()),
           "sar_slab_reduce_f32")
@@ -1123,24 +1165,18 @@ def pgc_backward(x, dout, q, saved, B, P, centers, variance, W, dx, g_centers, g
 PGPOOL_MAX = 512
 
 
-def _pgpool_check(B, P, C, J, cn=(), dense=()):
-    """ValueError before the library is touched: sizes the kernels are not built for, operands that are not float32 CUDA tensors,
-    `cn` operands (2-D, B * P live columns) without a unit column stride, `dense` operands that are not contiguous"""
+def _pgpool_check(B, P, C, J, cn, dense, i32=()):
+    """ValueError before the library is touched: sizes the kernels are not built for, then the `cn` operands (name -> CN matrix of
+    B * P columns), then the `dense` ones (name -> contiguous tensor), then all of them and `i32` on the GPU in their dtype"""
     if not (1 <= C <= PGPOOL_MAX and 1 <= J <= PGPOOL_MAX):
         raise ValueError("ProjectionGraphPool is built for 1 <= C <= %d and 1 <= J <= %d (got C = %d, J = %d)" % (PGPOOL_MAX, PGPOOL_MAX, C, J))
     if B < 1 or P < 1:
         raise ValueError("ProjectionGraphPool needs B >= 1 and P >= 1 (got B = %d, P = %d)" % (B, P))
-    for t in cn:
-        if not (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.shape[1] == B * P):
-            raise ValueError("a CN operand must be a 2-D tensor of B * P = %d columns, contiguous or a row-strided view with a unit "
-                             "column stride (got shape %s, strides %s)" % (B * P, tuple(t.shape), tuple(t.stride())))
-    for t in dense:
-        if not t.is_contiguous():
-            raise ValueError("a per-sample or parameter operand must be contiguous (got shape %s, strides %s)"
-                             % (tuple(t.shape), tuple(t.stride())))
-    for t in tuple(cn) + tuple(dense):
-        if not (t.is_cuda and t.dtype in (torch.float32, torch.int32)):
-            raise ValueError("operands must be float32 CUDA tensors (got %s on %s)" % (t.dtype, t.device))
+    for what, t in cn.items():
+        O.cn_matrix(t, None, B * P, what)
+    for what, t in dense.items():
+        O.dense(t, None, what)
+    O.on_gpu("ProjectionGraphPool", tuple(cn.values()) + tuple(dense.values()), i32)
 
 
 def pgpool_forward(x, B, P, centers, variance):
@@ -1148,15 +1184,13 @@ def pgpool_forward(x, B, P, centers, variance):
     (zn (B, C, J), A_out (B, J, J), saved): saved = (q [J][B*P], clamp bits, zp (B, C, J), qs (B, J), n2 (B, C), tab (4, C, J)) is what
     pgpool_backward needs."""
     C, J = x.shape[0], centers.numel() // max(x.shape[0], 1)
-    dev = x.device
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    _pgpool_check(B, P, C, J, cn=(x,), dense=(centers, variance))
+    _pgpool_check(B, P, C, J, dict(x=x), dict(centers=centers, variance=variance))
     if centers.numel() != C * J or variance.numel() != C * J:
         raise ValueError("centers / variance must hold C * J = %d elements each" % (C * J))
-    lib = L.load()
+    lib, new = L.load(), _new(x.device)
     q, tab, S, zn, A = new(J, B * P), new(4, C, J), new(B, C, J), new(B, C, J), new(B, J, J)
     qs, n2 = new(B, J), new(B, C)
-    clamp = torch.empty((B * P, lib.sar_pgpool_clamp_words(J)), dtype=torch.int32, device=dev)
+    clamp = _new(x.device, torch.int32)(B * P, lib.sar_pgpool_clamp_words(J))
     st = stream_ptr()
     check(lib.sar_pgpool_prep_f32(ptr(centers), ptr(variance), C, J, ptr(tab), st), "sar_pgpool_prep_f32")
     check(lib.sar_pgpool_assign_f32(ptr(x), x.stride(0), B, P, C, J, ptr(centers), ptr(tab), ptr(q), q.stride(0), ptr(clamp), st),
@@ -1173,14 +1207,14 @@ def pgpool_backward(x, B, P, centers, zn, saved, dz, dA, dx, dcenters, dvariance
     (C * J elements each) are written.  Returns dl [J][B*P]."""
     q, clamp, zp, qs, n2, tab = saved
     C, J = x.shape[0], q.shape[0]
-    dev = x.device
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    dev, new = x.device, _new(x.device)
     if dz is None:
         dz = torch.zeros((B, C, J), dtype=torch.float32, device=dev)
     if dA is None:
         dA = torch.zeros((B, J, J), dtype=torch.float32, device=dev)
     dq = new(J, B * P)
-    _pgpool_check(B, P, C, J, cn=(x, q, dx, dq), dense=(centers, zn, dz, dA, dcenters, dvariance))
+    _pgpool_check(B, P, C, J, dict(x=x, q=q, dx=dx, dq=dq), dict(centers=centers, zn=zn, dz=dz, dA=dA, dcenters=dcenters,
+                                                                 dvariance=dvariance), i32=(clamp,))
     if tuple(dz.shape) != (B, C, J) or tuple(dA.shape) != (B, J, J) or dcenters.numel() != C * J or dvariance.numel() != C * J:
         raise ValueError("dz must be (B, C, J), dA (B, J, J), dcenters / dvariance C * J elements")
     lib = L.load()
@@ -1218,33 +1252,6 @@ def gpool_keep(keeprate, V):
     return keep
 
 
-def _gpool_view(t, shape, what):
-    if not (isinstance(t, torch.Tensor) and t.dim() == 4 and tuple(t.shape) == tuple(shape)):
-        raise ValueError("%s must be a 4-D tensor of shape %s (got %s)" % (what, tuple(shape), tuple(t.shape) if hasattr(t, "shape") else t))
-    N, C, T, W = shape
-    sn, sc = t.stride(0), t.stride(1)
-    inner = (T == 1 or t.stride(2) == W) and (W == 1 or t.stride(3) == 1)
-    nchw = sc >= T * W and (C == 1 or N == 1 or sn >= C * sc)
-    cn = sn >= T * W and (N == 1 or C == 1 or sc >= N * sn)
-    if not (inner and (nchw or cn)):
-        raise ValueError("%s must have unit inner strides (W, 1) and be channel-major per sample (NCHW) or sample-major per channel (a CN "
-                         "matrix): got shape %s, strides %s" % (what, tuple(t.shape), tuple(t.stride())))
-    return sn, sc
-
-
-def _gpool_dense(t, shape, what):
-    if not (isinstance(t, torch.Tensor) and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
-        raise ValueError("%s must be a contiguous tensor of shape %s (got %s)" % (what, tuple(shape), tuple(t.shape) if hasattr(t, "shape") else t))
-
-
-def _gpool_device(f32=(), i32=()):
-    """after the shapes and strides: everything is on the GPU in its dtype"""
-    for ts, dtype in ((f32, torch.float32), (i32, torch.int32)):
-        for t in ts:
-            if not (t.is_cuda and t.dtype == dtype):
-                raise ValueError("GPool operands must be %s CUDA tensors (got %s on %s)" % (dtype, t.dtype, t.device))
-
-
 def _gpool_check(N, C, T, V, K):
     if not (1 <= V <= GPOOL_VMAX and 1 <= K <= GPOOL_KMAX):
         raise ValueError("GPool is built for 1 <= V <= %d and 1 <= K <= %d (got V = %d, K = %d)" % (GPOOL_VMAX, GPOOL_KMAX, V, K))
@@ -1266,20 +1273,18 @@ def gpool_forward(x, A, p, keeprate, out=None):
     K = A.shape[1]
     _gpool_check(N, C, T, V, K)
     keep = gpool_keep(keeprate, V)
-    sn, sc = _gpool_view(x, (N, C, T, V), "x")
-    _gpool_dense(A, (N, K, V, V), "A")
+    sn, sc = O.view4(x, (N, C, T, V), "x")
+    O.dense(A, (N, K, V, V), "A")
     if not (isinstance(p, torch.Tensor) and p.numel() == C * T):
         raise ValueError("projection_vector must hold C * T = %d elements" % (C * T))
-    _gpool_dense(p, tuple(p.shape), "projection_vector")
-    _gpool_device((x, A, p))
-    dev = x.device
+    O.dense(p, None, "projection_vector")
+    O.on_gpu("GPool", (x, A, p))
+    new, newi = _new(x.device), _new(x.device, torch.int32)
     if out is None:
-        out = torch.empty((N, C, T, keep), dtype=torch.float32, device=dev)
-    on, oc = _gpool_view(out, (N, C, T, keep), "out")
-    _gpool_device((out,))
+        out = new(N, C, T, keep)
+    on, oc = O.view4(out, (N, C, T, keep), "out")
+    O.on_gpu("GPool", (out,))
     lib = L.load()
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-    newi = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
     ph, norm, part = new(C * T), new(2), new(N, lib.sar_gpool_groups(C, T), V)
     y, s, idx, pos, A_out = new(N, V), new(N, keep), newi(N, keep), newi(N, V), new(N, K, keep, keep)
     st = stream_ptr()
@@ -1301,23 +1306,22 @@ def gpool_backward(x, A, saved, dout, dA_out, dx=None):
     N, C, T, V = x.shape
     K, keep = A.shape[1], idx.shape[1]
     _gpool_check(N, C, T, V, K)
-    sn, sc = _gpool_view(x, (N, C, T, V), "x")
-    _gpool_dense(A, (N, K, V, V), "A")
-    _gpool_dense(idx, (N, keep), "idx")
-    _gpool_dense(pos, (N, V), "pos")
-    dev = x.device
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    sn, sc = O.view4(x, (N, C, T, V), "x")
+    O.dense(A, (N, K, V, V), "A")
+    O.dense(idx, (N, keep), "idx")
+    O.dense(pos, (N, V), "pos")
+    new = _new(x.device)
     dp = dA = None
     if dout is not None:
-        dn, dc = _gpool_view(dout, (N, C, T, keep), "dout")
+        dn, dc = O.view4(dout, (N, C, T, keep), "dout")
         if dx is not None:
-            gn, gc = _gpool_view(dx, (N, C, T, V), "dx")
+            gn, gc = O.view4(dx, (N, C, T, V), "dx")
     if dA_out is not None:
-        _gpool_dense(dA_out, (N, K, keep, keep), "dA_out")
-    _gpool_device((x, A, y, s, ph, norm) + tuple(t for t in (dout, dA_out, dx) if t is not None), (idx, pos))
+        O.dense(dA_out, (N, K, keep, keep), "dA_out")
+    O.on_gpu("GPool", (x, A, y, s, ph, norm) + tuple(t for t in (dout, dA_out, dx) if t is not None), (idx, pos))
     if dout is not None and dx is None:
         dx = new(N, C, T, V)
-        gn, gc = _gpool_view(dx, (N, C, T, V), "dx")
+        gn, gc = O.view4(dx, (N, C, T, V), "dx")
     lib = L.load()
     st = stream_ptr()
     if dout is not None:
@@ -1337,7 +1341,7 @@ def gpool_backward(x, A, saved, dout, dA_out, dx=None):
 
 # ------------------------------------------------------------------------------------------------ TemporalAttention
 # csrc/tattn.hip (include/sar_hip.h: TemporalAttention).  x / out / dout / dx are 4-D (N, C, T, V) tensors or views whose two inner
-# strides are (V, 1), as GPool's.  params = [kernel_1, bias_1, .., kernel_L, bias_L] in the Keras layouts, kernel_i (in, units),
+# strides are (V, 1) (O.view4).  params = [kernel_1, bias_1, .., kernel_L, bias_L] in the Keras layouts, kernel_i (in, units),
 # in_1 = V C with row v C + c, units_L = 1.  The hidden activations are CN matrices [units][N T]
 TATTN_UMAX, TATTN_VMAX = 128, 64
 TATTN_RELU, TATTN_SIGMOID = 0, 1
@@ -1369,45 +1373,29 @@ def _tattn_check(x, params):
     return N, C, T, V, params
 
 
-def _tattn_device(ts):
-    for t in ts:
-        if not (t.is_cuda and t.dtype == torch.float32):
-            raise ValueError("TemporalAttention operands must be float32 CUDA tensors (got %s on %s)" % (t.dtype, t.device))
-
-
-def _tattn_geo(N, T):
-    """a (B, T', V') factorisation of the N T columns with V' <= 64 for the 1x1 products of the later layers"""
-    vf = max(d for d in range(1, min(T, 64) + 1) if T % d == 0)
-    return dict(B=N, V=vf, T_src=T // vf, T_out=T // vf)
-
-
 def tattn_forward(x, params, out=None):
     """TemporalAttention forward (models/stgcn.py:75-85) of x (N, C, T, V), a tensor or a strided view.  Returns (out, saved); `out` may
     be given as a view of the caller's buffer.  saved = (a (N T), h_1 (units_1, N T), .., h_{L-1}): the gate and the hidden
     activations, what tattn_backward needs besides x and params."""
     N, C, T, V, params = _tattn_check(x, params)
-    sn, sc = _gpool_view(x, (N, C, T, V), "x")
+    sn, sc = O.view4(x, (N, C, T, V), "x")
     if out is not None:
-        on, oc = _gpool_view(out, (N, C, T, V), "out")
-    _tattn_device([x] + params + ([out] if out is not None else []))
-    dev, n, nl = x.device, N * T, len(params) // 2
+        on, oc = O.view4(out, (N, C, T, V), "out")
+    O.on_gpu("TemporalAttention", [x] + params + ([out] if out is not None else []))
+    new, n, nl = _new(x.device), N * T, len(params) // 2
     if out is None:
-        out = torch.empty((N, C, T, V), dtype=torch.float32, device=dev)
-        on, oc = _gpool_view(out, (N, C, T, V), "out")
-    lib, st, geo = L.load(), stream_ptr(), _tattn_geo(N, T)
+        out = new(N, C, T, V)
+        on, oc = O.view4(out, (N, C, T, V), "out")
+    lib, st, geo = L.load(), stream_ptr(), column_geometry(N, T)      # (the later layers: 1x1 products over the N T columns)
     u = params[0].shape[1]
-    h = torch.empty((u, n), dtype=torch.float32, device=dev)
+    h = new(u, n)
     check(lib.sar_tattn_score_f32(ptr(x), sn, sc, ptr(params[0]), ptr(params[1]), N, C, T, V, u, TATTN_SIGMOID if nl == 1 else TATTN_RELU,
                                   ptr(h), n, st), "sar_tattn_score_f32")
     hs = []
     for i in range(1, nl):
         hs.append(h)
-        kernel, bias = params[2 * i], params[2 * i + 1]
-        cin, u = kernel.shape
-        z = torch.empty((u, n), dtype=torch.float32, device=dev)
-        conv_gemm(L.SAR_CONV_TEMPORAL, h, z, kernel, 0, u, Kc=cin, M=u, taps=1, stride=1, pad=0, bias=bias, split=None, **geo)
-        check(lib.sar_tattn_act_f32(ptr(z), n, u, n, TATTN_SIGMOID if i == nl - 1 else TATTN_RELU, st), "sar_tattn_act_f32")
-        h = z
+        h = conv1x1_fwd(h, params[2 * i], params[2 * i + 1], geo)
+        check(lib.sar_tattn_act_f32(ptr(h), n, h.shape[0], n, TATTN_SIGMOID if i == nl - 1 else TATTN_RELU, st), "sar_tattn_act_f32")
     a = h.view(n)
     check(lib.sar_tattn_scale_f32(ptr(x), sn, sc, ptr(a), N, C, T, V, ptr(out), on, oc, st), "sar_tattn_scale_f32")
     return out, (a,) + tuple(hs)
@@ -1419,49 +1407,42 @@ def tattn_backward(x, saved, params, dout, need_dx=True, dx=None, keep=None):
     gradient's product is not launched.  keep: a dict that receives the gradients at the last and the first pre-activation, "dz_L"
     (1, N T) and "dz_1" (units_1, N T), for the tests."""
     N, C, T, V, params = _tattn_check(x, params)
-    sn, sc = _gpool_view(x, (N, C, T, V), "x")
-    dn, dc = _gpool_view(dout, (N, C, T, V), "dout")
+    sn, sc = O.view4(x, (N, C, T, V), "x")
+    dn, dc = O.view4(dout, (N, C, T, V), "dout")
     if need_dx and dx is not None:
-        gn, gc = _gpool_view(dx, (N, C, T, V), "dx")
+        gn, gc = O.view4(dx, (N, C, T, V), "dx")
     n, nl = N * T, len(params) // 2
     a, hs = saved[0], list(saved[1:])
     if len(hs) != nl - 1 or a.numel() != n or any(tuple(h.shape) != (params[2 * i].shape[1], n) for i, h in enumerate(hs)):
         raise ValueError("saved does not belong to these params and this x")
-    _tattn_device([x, dout, a] + hs + params + ([dx] if need_dx and dx is not None else []))
-    dev = x.device
-    lib, st, geo = L.load(), stream_ptr(), _tattn_geo(N, T)
-    dz = torch.empty((1, n), dtype=torch.float32, device=dev)
+    O.on_gpu("TemporalAttention", [x, dout, a] + hs + params + ([dx] if need_dx and dx is not None else []))
+    new = _new(x.device)
+    lib, st, geo = L.load(), stream_ptr(), column_geometry(N, T)
+    dz = new(1, n)
     check(lib.sar_tattn_dscore_f32(ptr(x), sn, sc, ptr(dout), dn, dc, ptr(a), N, C, T, V, ptr(dz), st), "sar_tattn_dscore_f32")
     grads = [None] * len(params)
     if keep is not None:
         keep["dz_L"] = dz
     for i in range(nl - 1, 0, -1):
         kernel, h = params[2 * i], hs[i - 1]
-        cin, u = kernel.shape
-        flat = torch.empty(cin * u + u, dtype=torch.float32, device=dev)
-        conv_wgrad(L.SAR_CONV_TEMPORAL, h, dz, flat, Kc=cin, M=u, taps=1, stride=1, pad=0, w_stride_tap=0, w_stride_c=u, wsize=cin * u,
-                   bsize=u, split=None, **geo)
-        grads[2 * i], grads[2 * i + 1] = flat[:cin * u].view(cin, u), flat[cin * u:]
-        WT = torch.empty((u, cin), dtype=torch.float32, device=dev)
-        transpose(kernel, WT, 1, cin, u)
-        dh = torch.empty((cin, n), dtype=torch.float32, device=dev)
-        conv_gemm(L.SAR_CONV_TEMPORAL, dz, dh, WT, 0, cin, Kc=u, M=cin, taps=1, stride=1, pad=0, transposed=True, split=None, **geo)
-        check(lib.sar_tattn_dact_f32(ptr(h), n, ptr(dh), n, cin, n, st), "sar_tattn_dact_f32")
-        dz = dh
+        dW, grads[2 * i + 1] = conv1x1_wgrad(h, dz, geo)
+        grads[2 * i] = dW.view(kernel.shape)
+        dz = conv1x1_dgrad(dz, kernel, geo)
+        check(lib.sar_tattn_dact_f32(ptr(h), n, ptr(dz), n, kernel.shape[0], n, st), "sar_tattn_dact_f32")
     if keep is not None:
         keep["dz_1"] = dz
     kernel = params[0]
     u, size = kernel.shape[1], kernel.numel() + kernel.shape[1]
     nslab = lib.sar_tattn_wgrad_slabs(N, C, T, V)
-    slab, flat = torch.empty((nslab, size), dtype=torch.float32, device=dev), torch.empty(size, dtype=torch.float32, device=dev)
+    slab, flat = new(nslab, size), new(size)
     check(lib.sar_tattn_wgrad_f32(ptr(x), sn, sc, ptr(dz), n, N, C, T, V, u, ptr(slab), nslab, st), "sar_tattn_wgrad_f32")
     check(lib.sar_slab_reduce_f32(ptr(slab), nslab, size, size, ptr(flat), st), "sar_slab_reduce_f32")
     grads[0], grads[1] = flat[:kernel.numel()].view(kernel.shape), flat[kernel.numel():]
     if not need_dx:
         return None, grads
     if dx is None:
-        dx = torch.empty((N, C, T, V), dtype=torch.float32, device=dev)
-        gn, gc = _gpool_view(dx, (N, C, T, V), "dx")
+        dx = new(N, C, T, V)
+        gn, gc = O.view4(dx, (N, C, T, V), "dx")
     check(lib.sar_tattn_dx_f32(ptr(dout), dn, dc, ptr(a), ptr(kernel), ptr(dz), n, N, C, T, V, u, ptr(dx), gn, gc, st), "sar_tattn_dx_f32")
     return dx, grads
 
@@ -1470,18 +1451,18 @@ def tattn_backward(x, saved, params, dout, need_dx=True, dx=None, keep=None):
 # csrc/adjattn.hip (include/sar_hip.h: AdaptiveAdjacency).  X / dX: CN matrices [C][ld] with columns (n, t, v) -- the modules' to_cn(x)
 # or an engine's own matrix (a row-strided view with N T V live columns); A (K, V, V); the kernels in the Keras layout (1, 1, C, K Ce)
 # (or (C, K Ce)), channel k Ce + e of subset k; phi_bias (K Ce).  theta and phi are ONE 1x1 product on the stacked kernel [C][2 K Ce]
-# (theta's columns, then phi's; zeros in the bias of theta's half) per pass, through the helpers every layer of models/gcn.py uses.
+# (theta's columns, then phi's; zeros in the bias of theta's half) per pass: conv1x1_fwd / conv1x1_wgrad / conv1x1_dgrad.
 ADJATTN_VMAX, ADJATTN_KMAX, ADJATTN_EMAX = 32, 4, 512
 
 
-def _adjattn_check(X, N, T, V, A, theta_kernel, phi_kernel, phi_bias=None, dense=()):
-    """ValueError before the library is touched -> (C, K, Ce)"""
-    ts = [X, A, theta_kernel, phi_kernel] + ([phi_bias] if phi_bias is not None else []) + list(dense)
-    if not all(isinstance(t, torch.Tensor) for t in ts):
+def _adjattn_check(X, N, T, V, A, theta_kernel, phi_kernel, phi_bias=None, **dense):
+    """ValueError before the library is touched -> (C, K, Ce); dense: further contiguous operands by name"""
+    rest = dict(A=A, theta_kernel=theta_kernel, phi_kernel=phi_kernel, **({} if phi_bias is None else dict(phi_bias=phi_bias)), **dense)
+    if not all(isinstance(t, torch.Tensor) for t in (X, *rest.values())):
         raise ValueError("AdaptiveAdjacency operands must be tensors")
-    if min(N, T, V) < 1 or not (X.dim() == 2 and X.shape[0] >= 1 and X.shape[1] == N * T * V and X.stride(1) == 1 and X.stride(0) >= X.shape[1]):
-        raise ValueError("X must be a CN matrix [C][N T V = %d columns], contiguous or a row-strided view with a unit column stride (got "
-                         "shape %s, strides %s)" % (N * T * V, tuple(X.shape), tuple(X.stride())))
+    if min(N, T, V) < 1:
+        raise ValueError("AdaptiveAdjacency needs N, T, V >= 1 (got N = %d, T = %d, V = %d)" % (N, T, V))
+    O.cn_matrix(X, None, N * T * V, "X")
     C = X.shape[0]
     if not (A.dim() == 3 and tuple(A.shape[1:]) == (V, V)):
         raise ValueError("A must be (K, V, V) = (K, %d, %d), got %s" % (V, V, tuple(A.shape)))
@@ -1499,12 +1480,9 @@ def _adjattn_check(X, N, T, V, A, theta_kernel, phi_kernel, phi_bias=None, dense
     if N * T * V >= 1 << 22 or N * K > 65535:
         raise ValueError("AdaptiveAdjacency is built for N T V < 2^22 columns (the 1x1 product) and N K <= 65535 (got N = %d, T = %d, V = %d, "
                          "K = %d)" % (N, T, V, K))
-    for t in ts[1:]:
-        if not t.is_contiguous():
-            raise ValueError("a parameter or per-sample operand must be contiguous (got shape %s, strides %s)" % (tuple(t.shape), tuple(t.stride())))
-    for t in ts:
-        if not (t.is_cuda and t.dtype == torch.float32):
-            raise ValueError("AdaptiveAdjacency operands must be float32 CUDA tensors (got %s on %s)" % (t.dtype, t.device))
+    for what, t in rest.items():
+        O.dense(t, None, what)
+    O.on_gpu("AdaptiveAdjacency", (X, *rest.values()))
     return C, K, kce // K
 
 
@@ -1517,12 +1495,10 @@ def adjattn_forward(X, N, T, V, A, theta_kernel, phi_kernel, phi_bias, keep=None
     saved = (E [2 K Ce][N T V]: theta's rows, then phi's; P (N, K, V, V)) is what adjattn_backward needs besides X and the kernels.
     keep: a dict that receives the logits "S" (N, K, V, V), for the tests."""
     C, K, Ce = _adjattn_check(X, N, T, V, A, theta_kernel, phi_kernel, phi_bias)
-    from models.gcn import _conv1x1_fwd       # (models.gcn imports this module: the helpers are looked up at the call)
-    dev, kce = X.device, K * Ce
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    new, kce = _new(X.device), K * Ce
     lib, st = L.load(), stream_ptr()
-    bias = torch.cat([torch.zeros(kce, dtype=torch.float32, device=dev), phi_bias])
-    E = _conv1x1_fwd(X, _adjattn_stacked(theta_kernel, phi_kernel, C), bias, dict(B=N, V=V, T_src=T, T_out=T))
+    bias = torch.cat([torch.zeros(kce, dtype=torch.float32, device=X.device), phi_bias])
+    E = conv1x1_fwd(X, _adjattn_stacked(theta_kernel, phi_kernel, C), bias, dict(B=N, V=V, T_src=T, T_out=T))
     S, P, A_eff = new(N, K, V, V), new(N, K, V, V), new(N, K, V, V)
     nslab = lib.sar_adjattn_sim_slabs(Ce, T, V)
     slab = new(nslab, N * K * V * V) if nslab > 1 else None
@@ -1543,21 +1519,18 @@ def adjattn_backward(X, N, T, V, saved, theta_kernel, phi_kernel, dA_eff, need_d
     if not (isinstance(E, torch.Tensor) and isinstance(theta_kernel, torch.Tensor) and theta_kernel.dim() >= 2 and P.shape[0] == N
             and tuple(E.shape) == (2 * theta_kernel.shape[-1], N * T * V)):
         raise ValueError("saved does not belong to these kernels and this X")
-    C, K, Ce = _adjattn_check(X, N, T, V, P[0], theta_kernel, phi_kernel, dense=(E, P, dA_eff))
-    kce, n = K * Ce, N * T * V
-    from models.gcn import _conv1x1_dgrad, _conv1x1_wgrad
-    dev = X.device
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    C, K, Ce = _adjattn_check(X, N, T, V, P[0], theta_kernel, phi_kernel, E=E, P=P, dA_eff=dA_eff)
+    kce, n, new = K * Ce, N * T * V, _new(X.device)
     lib, st, geo = L.load(), stream_ptr(), dict(B=N, V=V, T_src=T, T_out=T)
     dS, dA, dE = new(N, K, V, V), (new(K, V, V) if need_dA else None), new(2 * kce, n)
     check(lib.sar_adjattn_softmax_bwd_f32(ptr(P), ptr(dA_eff), N, K, V, ptr(dS), ptr(dA), st), "sar_adjattn_softmax_bwd_f32")
     check(lib.sar_adjattn_dembed_f32(ptr(dS), ptr(E), ptr(E[kce:]), n, N, K, Ce, T, V, ptr(dE), ptr(dE[kce:]), n, st), "sar_adjattn_dembed_f32")
     if keep is not None:
         keep["dS"], keep["dE"] = dS, dE
-    dW, db = _conv1x1_wgrad(X, dE, geo)
+    dW, db = conv1x1_wgrad(X, dE, geo)
     dW = dW.view(C, 2 * kce)
     dtk, dpk = dW[:, :kce].contiguous().view(theta_kernel.shape), dW[:, kce:].contiguous().view(phi_kernel.shape)
-    dX = _conv1x1_dgrad(dE, _adjattn_stacked(theta_kernel, phi_kernel, C), geo) if need_dx else None
+    dX = conv1x1_dgrad(dE, _adjattn_stacked(theta_kernel, phi_kernel, C), geo) if need_dx else None
     return dX, dtk, dpk, db[kce:], dA
 
 

@@ -1,7 +1,7 @@
 """Records what crosses the C ABI (include/sar_hip.h) while the tensor-level wrappers of sar_amd run on CPU tensors: a proxy that
 stands in for the loaded library, passes the host-only query entry points through to it and records every other call WITHOUT
-launching anything -- on a machine with a GPU as well as on one without.  A helper of tests/test_conv_launch_abi.py and
-tests/golden/make_golden_conv_launch_abi.py, not a test.
+launching anything -- on a machine with a GPU as well as on one without.  A helper of tests/test_conv_launch_abi.py,
+tests/test_layer_launch_abi.py and their generators under tests/golden/, not a test.
 
     with AbiTrace() as tr:
         ops.conv_gemm(...)
@@ -29,7 +29,7 @@ from sar_amd import _lib as L  # noqa: E402
 from sar_amd import ops, ops8  # noqa: E402
 
 # entry points that only compute a number on the host: passed through, not recorded
-_QUERY_SUFFIXES = ("_nparts", "_blocks", "_bytes", "_floats", "_frames", "_groups", "_words")
+_QUERY_SUFFIXES = ("_nparts", "_blocks", "_bytes", "_floats", "_frames", "_groups", "_words", "_slabs")
 _QUERY_NAMES = ("sar_struct_size", "sar_version", "sar_last_error_string")
 # the item table of a batched launch: (its argument, the argument that counts its items, the item's record, the pointer fields)
 _TABLES = {

@@ -416,7 +416,8 @@ def record(fn):
 digest, first_difference = S.digest, S.first_difference
 
 
-if __name__ == "__main__":
+def write_fixture(out, commit, cases, FULL, generator):
+    """the fixture of `generator` (a module's name): the digest of every case of cases(), the traces of the cases named in FULL"""
     torch.set_num_threads(min(16, torch.get_num_threads()))
     digests, full, seen = {}, {}, set()
     for group, name, fn in cases():
@@ -427,13 +428,17 @@ if __name__ == "__main__":
         if name in FULL:
             full[name] = calls
     assert set(full) == set(FULL), set(FULL) - set(full)
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "conv_launch_abi.json")
     header = ("recorded at commit %s with no SAR_* knob set, on a machine without a GPU; digests: three hex digits per recorded call, "
-              "per group the cases in the order of make_golden_conv_launch_abi.cases()" % COMMIT)
+              "per group the cases in the order of %s.cases()" % (commit, generator))
     with open(out, "w") as fh:
-        fh.write('{"header": %s,\n"commit": %s,\n"digests": {\n' % (json.dumps(header), json.dumps(COMMIT))
+        fh.write('{"header": %s,\n"commit": %s,\n"digests": {\n' % (json.dumps(header), json.dumps(commit))
                  + ",\n".join("%s: [\n%s\n]" % (json.dumps(g), ",\n".join(json.dumps(d) for d in v)) for g, v in digests.items())
                  + '\n},\n"traces": {\n'
                  + ",\n".join("%s: [\n  %s\n]" % (json.dumps(k), ",\n  ".join(json.dumps(e, sort_keys=True) for e in v))
                               for k, v in full.items()) + "\n}}\n")
     print("wrote %d cases in %d groups, %d full traces, %d bytes" % (len(seen), len(digests), len(full), os.path.getsize(out)))
+
+
+if __name__ == "__main__":
+    write_fixture(sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "conv_launch_abi.json"), COMMIT, cases, FULL,
+                  "make_golden_conv_launch_abi")

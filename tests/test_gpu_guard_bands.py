@@ -682,7 +682,7 @@ def pgc_case(B, T):
 
 @pytest.mark.parametrize("pad", PADS)
 def test_projection_graph_convolution(dev, pad):
-    """pgc_forward / pgc_backward at B, T = 3, 17 with x, dout, out and dx padded (ops._pgc_args: any ld >= B P).  Bars: 1e-4, and for
+    """pgc_forward / pgc_backward at B, T = 3, 17 with x, dout, out and dx padded (operands.cn_matrix: any ld >= B P).  Bars: 1e-4, and for
     the two all-column sums eight times the float32 restatement's own distance from float64 (tests/test_gpu_stpgcn.py: _judge)."""
     from sar_amd import ops
     B, T = 3, 17

@@ -458,7 +458,7 @@ def test_rejected_calls_launch_nothing(dev):
 
 
 def test_wrappers_raise_value_error_before_the_library(dev, monkeypatch):
-    """ops._pgc_args: what was an assert is a ValueError (as ops._pgpool_check), raised before anything is allocated or launched"""
+    """the operand checks of sar_amd/operands.py (O.on_gpu, O.cn_matrix): a ValueError, raised before anything is allocated or launched"""
     from sar_amd import _lib, ops
     a = setup(("init", 2, 128))
     B, P = a.B, a.P

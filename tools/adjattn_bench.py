@@ -30,7 +30,7 @@ def torch_layer(x, A, tk, pk, pb):
 
 def main():
     from models.agcn import AdaptiveAdjacency
-    from models.gcn import _conv1x1_dgrad, _conv1x1_fwd, _conv1x1_wgrad, to_cn
+    from models.gcn import to_cn
     from sar_amd import _lib as L
     from sar_amd import box, ops
     from sar_amd._lib import check, ptr, stream_ptr
@@ -117,13 +117,13 @@ def main():
         nslab = lib.sar_adjattn_sim_slabs(Ce, T, V)
         slab = new(nslab, N * K * V * V)
         each = {
-            "1x1 fwd": lambda: _conv1x1_fwd(X, W, bias, geo, out=E2),
+            "1x1 fwd": lambda: ops.conv1x1_fwd(X, W, bias, geo, out=E2),
             "sim": lambda: check(lib.sar_adjattn_sim_f32(ptr(E), ptr(E[kce:]), n, N, K, Ce, T, V, ptr(S), ptr(slab), nslab, st)),
             "softmax": lambda: check(lib.sar_adjattn_softmax_f32(ptr(S), ptr(A), N, K, V, ptr(P2), ptr(A2), st)),
             "softmax_bwd": lambda: check(lib.sar_adjattn_softmax_bwd_f32(ptr(P), ptr(dA_eff), N, K, V, ptr(dS2), ptr(dA2), st)),
             "dembed": lambda: check(lib.sar_adjattn_dembed_f32(ptr(dS), ptr(E), ptr(E[kce:]), n, N, K, Ce, T, V, ptr(dE2), ptr(dE2[kce:]), n, st)),
-            "1x1 wgrad": lambda: _conv1x1_wgrad(X, dE, geo),
-            "1x1 dgrad": lambda: _conv1x1_dgrad(dE, W, geo),
+            "1x1 wgrad": lambda: ops.conv1x1_wgrad(X, dE, geo),
+            "1x1 dgrad": lambda: ops.conv1x1_dgrad(dE, W, geo),
             "to_cn(x)": lambda: to_cn(x),
         }
         for f in each.values():
