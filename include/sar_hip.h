@@ -1096,6 +1096,41 @@ int sar_adjattn_dembed_f32(const float* dS, const float* theta, const float* phi
                            float* dtheta, float* dphi, int64_t ld_d, sar_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
+ * TemporalConv: Keras Conv2D(M, [k, 1], strides=[s, 1], dilation_rate=[d, 1], data_format='channels_first') with k, d, s and the
+ * left padding as run-time arguments (the temporal unit of MS-G3D / CTR-GCN / InfoGCN / HD-GCN; sar_conv_gemm_f32 is built for 9 taps
+ * and 1 tap, no dilation).  csrc/tconv.hip, fp32; the three products run on v_mfma_f32_32x32x2_f32.
+ * x, dx: (N, C, T, V); out, dout: (N, M, T_out, V); each passed as (pointer, s_n, s_c): element (n, c, t, v) at n*s_n + c*s_c + t*V + v
+ * -- NCHW: s_n = C*T*V, s_c = T*V; a CN matrix [C][ld]: s_n = T*V, s_c = ld (as GPool and TemporalAttention above).  The runs of T*V
+ * floats may not overlap.  kernel: the Keras kernel (k, 1, C, M) contiguous, W[j][c][m]; bias (M).
+ *   out[n,m,to,v] = bias[m] + sum_{j<k} sum_{c<C} W[j][c][m] x[n, c, to*s + j*d - pad, v], x read as exactly 0 outside [0, T)
+ * Limits: 1 <= k <= SAR_TCONV_KMAX, 1 <= d <= SAR_TCONV_DMAX, s in {1, 2}, 0 <= pad <= (k-1)*d, 1 <= C, M <= SAR_TCONV_CMAX,
+ * 1 <= V <= SAR_TCONV_VMAX, N <= 65535, fewer than 2^31 elements per tensor: SAR_E_UNSUP outside.  SAR_E_ARG: a NULL operand, a size
+ * below 1, strides that do not describe the tensor (an ld shorter than its row), an output that is an input, and a T_out whose last
+ * window passes the last frame by more than pad + 1 frames ((T_out-1)*s + (k-1)*d - pad > T + pad; SAME puts its odd frame of padding
+ * behind).  Every error is returned before any launch.  No size need be a multiple of a tile.  No atomics: repeated launches are
+ * bitwise equal, and a sample's out / dx depend on the sample's data only.
+ *   sar_tconv_fwd_f32       out as above; bias may be NULL.  Every element of out is written once
+ *   sar_tconv_bwd_data_f32  dx[n,c,u,v] = sum_j sum_m W[j][c][m] dout[n, m, (u + pad - j*d)/s, v] over the j whose quotient is exact and
+ *                           in [0, T_out) (the gather form).  kernel_t is the (k, M, C) image of the kernel, kernel_t[j][m][c] =
+ *                           W[j][c][m]: sar_transpose_f32(kernel, kernel_t, k, C, M).  Every element of dx is written, zeros included;
+ *                           with s = 2 only the taps whose parity meets an output frame are issued
+ *   sar_tconv_wgrad_f32     slab[i] = this slab's share of dW (k, 1, C, M) | dbias (M): dW[j][c][m] = sum_{n,to,v} x[n, c, to*s + j*d -
+ *                           pad, v] dout[n,m,to,v], dbias[m] = sum dout.  nslab = sar_tconv_wgrad_slabs(N, C, M, T_out, V) (a function
+ *                           of the shape alone); slab stride k*C*M + M; every element of every slab is written; add the slabs with
+ *                           sar_slab_reduce_f32 */
+#define SAR_TCONV_KMAX 9
+#define SAR_TCONV_DMAX 8
+#define SAR_TCONV_CMAX 512
+#define SAR_TCONV_VMAX 64
+int sar_tconv_fwd_f32(const float* x, int64_t s_n, int64_t s_c, const float* kernel, const float* bias, int N, int C, int M, int T, int T_out,
+                      int V, int k, int d, int s, int pad, float* out, int64_t o_sn, int64_t o_sc, sar_stream_t st);
+int sar_tconv_bwd_data_f32(const float* dout, int64_t d_sn, int64_t d_sc, const float* kernel_t, int N, int C, int M, int T, int T_out, int V,
+                           int k, int d, int s, int pad, float* dx, int64_t g_sn, int64_t g_sc, sar_stream_t st);
+int sar_tconv_wgrad_slabs(int N, int C, int M, int T_out, int V);
+int sar_tconv_wgrad_f32(const float* x, int64_t s_n, int64_t s_c, const float* dout, int64_t d_sn, int64_t d_sc, int N, int C, int M, int T,
+                        int T_out, int V, int k, int d, int s, int pad, float* slab, int nslab, sar_stream_t st);
+
+/* ------------------------------------------------------------------------------------------------
  * Box calibration (csrc/box_probe.hip; bench.py's "box" object -- no reference counterpart, measurement only): what the box
  * this process landed on sustains, so that a line's `frac` (against the guide's peaks) can be read next to `frac_of_box`.
  *   sar_box_mfma        dense loop of one matrix instruction: kind 0 = v_mfma_f32_32x32x2_f32, 1 = v_mfma_f32_32x32x16_f16,

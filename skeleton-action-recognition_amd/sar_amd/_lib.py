@@ -260,6 +260,11 @@ SIGNATURES = {
     "sar_adjattn_softmax_f32": (_i, [_fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
     "sar_adjattn_softmax_bwd_f32": (_i, [_fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
     "sar_adjattn_dembed_f32": (_i, [_fp, _fp, _fp, _i64, _i, _i, _i, _i, _i, _fp, _fp, _i64, _fp]),
+    # TemporalConv: a temporal convolution with run-time kernel size, dilation and stride, its gradients (csrc/tconv.hip)
+    "sar_tconv_fwd_f32": (_i, [_fp, _i64, _i64, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _i64, _i64, _fp]),
+    "sar_tconv_bwd_data_f32": (_i, [_fp, _i64, _i64, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _i64, _i64, _fp]),
+    "sar_tconv_wgrad_slabs": (_i, [_i, _i, _i, _i, _i]),
+    "sar_tconv_wgrad_f32": (_i, [_fp, _i64, _i64, _fp, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _i, _fp]),
     # box calibration (bench.py "box"; csrc/box_probe.hip)
     "sar_box_mfma": (_i, [_i, _i, _i, _fp, _fp, _fp]),
     "sar_box_mfma_flops": (_i64, [_i, _i, _i]),

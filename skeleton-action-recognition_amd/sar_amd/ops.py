@@ -1534,6 +1534,137 @@ def adjattn_backward(X, N, T, V, saved, theta_kernel, phi_kernel, dA_eff, need_d
     return dX, dtk, dpk, db[kce:], dA
 
 
+# ------------------------------------------------------------------------------------------------ TemporalConv
+# csrc/tconv.hip (include/sar_hip.h: TemporalConv).  x / dx (N, C, T, V) and out / dout (N, M, T_out, V) are 4-D tensors or views whose
+# two inner strides are (V, 1) (O.view4): NCHW tensors and the view of an engine's CN matrix run the same kernels.  kernel: the Keras
+# kernel (k, 1, C, M), contiguous; bias (M) or None.
+TCONV_KMAX, TCONV_DMAX, TCONV_CMAX, TCONV_VMAX = 9, 8, 512, 64
+
+
+def tconv_geometry(T, k, s, d, padding):
+    """(T_out, pad) of a temporal convolution of T frames with k taps, stride s and dilation d.  padding="same": TensorFlow's SAME with
+    the dilated extent (the odd frame of padding goes behind; at k = 9, d = 1 this is sar_amd.stgcn.same_pad); padding=p (an int):
+    PyTorch's symmetric padding of p frames."""
+    T, k, s, d = int(T), int(k), int(s), int(d)
+    if min(T, k, s, d) < 1:
+        raise ValueError("tconv_geometry needs T, k, s, d >= 1 (got %d, %d, %d, %d)" % (T, k, s, d))
+    if padding == "same":
+        T_out = -(-T // s)
+        return T_out, max((T_out - 1) * s + (k - 1) * d + 1 - T, 0) // 2
+    if isinstance(padding, bool) or not isinstance(padding, int) or padding < 0:
+        raise ValueError("padding must be \"same\" or a number of frames >= 0 (got %r)" % (padding,))
+    T_out = (T + 2 * padding - d * (k - 1) - 1) // s + 1
+    if T_out < 1:
+        raise ValueError("no output frame: T = %d, k = %d, d = %d with padding %d" % (T, k, d, padding))
+    return T_out, padding
+
+
+def tconv_limits(k, d, s, pad=0, C=1, M=1, V=1, N=1):
+    """ValueError for what csrc/tconv.hip is not built for"""
+    if not (1 <= k <= TCONV_KMAX and 1 <= d <= TCONV_DMAX and s in (1, 2) and 0 <= pad <= (k - 1) * d):
+        raise ValueError("TemporalConv is built for 1 <= kernel_size <= %d, 1 <= dilation <= %d, stride 1 or 2 and 0 <= pad <= (k - 1) d "
+                         "(got kernel_size = %d, dilation = %d, stride = %d, pad = %d)" % (TCONV_KMAX, TCONV_DMAX, k, d, s, pad))
+    if not (1 <= C <= TCONV_CMAX and 1 <= M <= TCONV_CMAX and 1 <= V <= TCONV_VMAX and 1 <= N <= 65535):
+        raise ValueError("TemporalConv is built for 1 <= C, filters <= %d, 1 <= V <= %d and 1 <= N <= 65535 (got C = %d, filters = %d, V = %d, "
+                         "N = %d)" % (TCONV_CMAX, TCONV_VMAX, C, M, V, N))
+
+
+def _tconv_check(x_shape, M, T_out, kernel, bias, s, d, pad):
+    """every limit of the three entry points -> (N, C, T, V, k); kernel None: the weight gradient, which takes k from M = (k, M)"""
+    if len(x_shape) != 4:
+        raise ValueError("x must be 4-D (N, C, T, V), got shape %s" % (tuple(x_shape),))
+    N, C, T, V = (int(v) for v in x_shape)
+    if kernel is not None:
+        if not (torch.is_tensor(kernel) and kernel.dim() == 4 and kernel.shape[1] == 1 and kernel.shape[2] == C):
+            raise ValueError("kernel must be the Keras kernel (k, 1, C, filters) = (k, 1, %d, filters), got %s"
+                             % (C, tuple(kernel.shape) if torch.is_tensor(kernel) else type(kernel).__name__))
+        k, M = int(kernel.shape[0]), int(kernel.shape[3])
+        O.dense(kernel, None, "kernel")
+    else:
+        k, M = M
+    s, d, pad, T_out = int(s), int(d), int(pad), int(T_out)
+    if min(N, C, T, V, M, T_out) < 1:
+        raise ValueError("TemporalConv needs a non-empty x, filters >= 1 and T_out >= 1 (got x %s, filters = %d, T_out = %d)" % (tuple(x_shape), M, T_out))
+    tconv_limits(k, d, s, pad, C, M, V, N)
+    if N * C * T * V >= 1 << 31 or N * M * T_out * V >= 1 << 31:
+        raise ValueError("TemporalConv is built for fewer than 2^31 elements per tensor (got x %s, filters = %d, T_out = %d)" % (tuple(x_shape), M, T_out))
+    if (T_out - 1) * s + (k - 1) * d - pad > T + pad:
+        raise ValueError("T_out = %d reads past what pad = %d allows (T = %d, kernel_size = %d, dilation = %d, stride = %d)" % (T_out, pad, T, k, d, s))
+    if bias is not None:
+        O.dense(bias, (M,), "bias")
+    return N, C, T, V, k, M
+
+
+def tconv_forward(x, kernel, bias, stride, dilation, pad, T_out, out=None):
+    """out[n,m,to,v] = bias[m] + sum_{j,c} kernel[j,0,c,m] x[n, c, to stride + j dilation - pad, v] (x is 0 outside [0, T)) of
+    x (N, C, T, V), a tensor or a strided view; bias may be None.  Returns out (N, M, T_out, V), which may be given as a view of the
+    caller's buffer.  One launch."""
+    if not torch.is_tensor(x):
+        raise ValueError("x must be a tensor")
+    N, C, T, V, k, M = _tconv_check(x.shape, None, T_out, kernel, bias, stride, dilation, pad)
+    sn, sc = O.view4(x, (N, C, T, V), "x")
+    if out is not None:
+        on, oc = O.view4(out, (N, M, T_out, V), "out")
+    O.on_gpu("TemporalConv", [x, kernel] + [t for t in (bias, out) if t is not None])
+    if out is None:
+        out = torch.empty((N, M, T_out, V), dtype=torch.float32, device=x.device)
+        on, oc = O.view4(out, (N, M, T_out, V), "out")
+    flops, nbytes = 2.0 * M * C * k * N * T_out * V, 4.0 * (N * C * T * V + N * M * T_out * V + k * C * M)
+    with profiler.region("tconv_fwd", flops, nbytes):
+        check(L.load().sar_tconv_fwd_f32(ptr(x), sn, sc, ptr(kernel), ptr(bias), N, C, M, T, T_out, V, k, int(dilation), int(stride), int(pad),
+                                         ptr(out), on, oc, stream_ptr()), "sar_tconv_fwd_f32")
+    return out
+
+
+def tconv_backward_data(dout, kernel, T, stride, dilation, pad, dx=None):
+    """dx (N, C, T, V) of tconv_forward from dout (N, M, T_out, V), a tensor or a strided view; every element of dx is written, and dx
+    may be given as a view of the caller's buffer.  Two launches: the (k, M, C) image of the kernel, the product."""
+    if not (torch.is_tensor(dout) and dout.dim() == 4 and torch.is_tensor(kernel) and kernel.dim() == 4):
+        raise ValueError("dout must be 4-D (N, filters, T_out, V) and kernel (k, 1, C, filters)")
+    N, Md, T_out, V = dout.shape
+    if kernel.shape[3] != Md:
+        raise ValueError("dout has %d channels, the kernel %d filters" % (Md, kernel.shape[3]))
+    N, C, T, V, k, M = _tconv_check((N, kernel.shape[2], T, V), None, T_out, kernel, None, stride, dilation, pad)
+    dn, dc = O.view4(dout, (N, M, T_out, V), "dout")
+    if dx is not None:
+        gn, gc = O.view4(dx, (N, C, T, V), "dx")
+    O.on_gpu("TemporalConv", [dout, kernel] + ([dx] if dx is not None else []))
+    if dx is None:
+        dx = torch.empty((N, C, T, V), dtype=torch.float32, device=dout.device)
+        gn, gc = O.view4(dx, (N, C, T, V), "dx")
+    kt = torch.empty((k, M, C), dtype=torch.float32, device=dout.device)
+    transpose(kernel, kt, k, C, M)
+    flops, nbytes = 2.0 * M * C * k * N * T_out * V, 4.0 * (N * C * T * V + N * M * T_out * V + k * C * M)
+    with profiler.region("tconv_bwd_data", flops, nbytes):
+        check(L.load().sar_tconv_bwd_data_f32(ptr(dout), dn, dc, ptr(kt), N, C, M, T, T_out, V, k, int(dilation), int(stride), int(pad), ptr(dx),
+                                              gn, gc, stream_ptr()), "sar_tconv_bwd_data_f32")
+    return dx
+
+
+def tconv_wgrad(x, dout, kernel_size, stride, dilation, pad):
+    """(dkernel (k, 1, C, M), dbias (M)) of tconv_forward from x (N, C, T, V) and dout (N, M, T_out, V), tensors or strided views.  Two
+    launches: the slabs' partials, their sum in slab order."""
+    if not (torch.is_tensor(x) and x.dim() == 4 and torch.is_tensor(dout) and dout.dim() == 4):
+        raise ValueError("x must be 4-D (N, C, T, V) and dout 4-D (N, filters, T_out, V)")
+    M, T_out = int(dout.shape[1]), int(dout.shape[2])
+    N, C, T, V, k, M = _tconv_check(x.shape, (int(kernel_size), M), T_out, None, None, stride, dilation, pad)
+    sn, sc = O.view4(x, (N, C, T, V), "x")
+    dn, dc = O.view4(dout, (N, M, T_out, V), "dout")
+    O.on_gpu("TemporalConv", [x, dout])
+    lib, st, size = L.load(), stream_ptr(), k * C * M + M
+    nslab = lib.sar_tconv_wgrad_slabs(N, C, M, T_out, V)
+    if nslab < 1:
+        check(nslab or -1, "sar_tconv_wgrad_slabs")
+    slab = torch.empty((nslab, size), dtype=torch.float32, device=x.device)
+    flat = torch.empty(size, dtype=torch.float32, device=x.device)
+    flops, nbytes = 2.0 * M * C * k * N * T_out * V, 4.0 * (N * C * T * V + N * M * T_out * V + k * C * M)
+    with profiler.region("tconv_wgrad", flops, nbytes):
+        check(lib.sar_tconv_wgrad_f32(ptr(x), sn, sc, ptr(dout), dn, dc, N, C, M, T, T_out, V, k, int(dilation), int(stride), int(pad), ptr(slab),
+                                      nslab, st), "sar_tconv_wgrad_f32")
+        check(lib.sar_slab_reduce_f32(ptr(slab), nslab, size, size, ptr(flat), st), "sar_slab_reduce_f32")
+    return flat[:k * C * M].view(k, 1, C, M), flat[k * C * M:]
+
+
 # ------------------------------------------------------------------------------------------------ ResNet-18 ops
 def _shape_tag(geo):
     """SAR_PROFILE_SHAPES=1 (diagnostic, tools/pathb_layers.py): one profiler bucket per layer geometry"""
